@@ -24,6 +24,8 @@ Prints ONE JSON line on rank 0, including
   also         -- (default cfg2 run on one GPU only) the 224^2 configurations of BASELINE.json measured in the same process:
                   the single-GPU shards of configs[3] (cfg4) and configs[4] (cfg5), a few hipGraph replays each, with the
                   conv family's roofline fraction.  They never enter `value`.
+  dump_outputs -- (--dump-outputs DIR only) the .npy files written after the timed steps: the last timed step's result vector
+                  and (a fixed sample of) its parameter and gradient arenas, for comparing two builds output for output.
 """
 import hashlib
 import os as _os
@@ -42,6 +44,8 @@ sys.path.insert(0, ROOT)
 MFMA_PEAK_BF16 = 2500.0  # TFLOP/s dense, /opt/skills/guides/MI355X_MICROARCH.md:42
 MFMA_PEAK_F32 = 157.3    # ibid. :41
 HBM_PEAK_GBS = 8000.0    # ibid. :35
+
+DUMP_SAMPLE = 1 << 22    # --dump-outputs: elements kept per parameter-sized array (2 x 16 MB of f32 at most)
 
 CONFIGS = {  # BASELINE.json "configs" -> per-GPU shard
     "cfg2": dict(net="resnet18", img_dim=128, pred_step=3, batch=128),
@@ -108,6 +112,29 @@ def live_pmc_traffic(config="cfg2", timeout_s=90):
         return None, f"{type(e).__name__}: {str(e)[:160]}"
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+def dump_outputs(out_dir, eng, res):
+    """--dump-outputs: what the timed path handed back in its last step, as float32 ``out_dir/<name>.npy``:
+      result -- [loss, top1, top3, top5], the step's return value
+      params -- the flat f32 parameter arena after that step's Adam update
+      grads  -- the flat f32 gradient arena of that step (after the all-reduce on more than one rank)
+    An arena of more than DUMP_SAMPLE elements is written as a fixed sample: the same seeded, sorted indices in every run, so
+    two builds can be compared output for output.  Returns the `dump_outputs` object of the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = eng.flat_p.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values.to(eng.flat_p.device)
+    arrays = {"result": res, "params": eng.flat_p if idx is None else eng.flat_p[idx],
+              "grads": eng.flat_g if idx is None else eng.flat_g[idx]}
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return {"dir": out_dir, "arrays": shapes, "arena_numel": n, "sampled": idx is not None}
 
 
 def score_block(eng, sc, steps, peak):
@@ -373,7 +400,12 @@ def main():
                          "falls back to the tracked profiles/*_pmc_traffic.json, flagged); file = the tracked profile only; off = null")
     ap.add_argument("--score-path", default="auto", choices=["auto", "fused", "materialised"],
                     help="contrastive score + loss: fused (no [R][R] tensor in HBM) or materialised; auto = materialised (the faster one at cfg2 and at cfg5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs); "
+                         "the same arguments give the same inputs in every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     for k in ("batch", "net", "img_dim", "pred_step"):
         if getattr(args, k) is not None:
@@ -424,6 +456,7 @@ def main():
     del init
     g = torch.Generator(dev).manual_seed(1234 + rank)
     block = torch.randn(batch, 8, 3, 5, img, img, device=dev, generator=g)
+    torch.cuda.manual_seed(1234 + rank)   # --fresh-input draws from the default generator: the same blocks in every run
     allreduce = make_allreduce(dist, world, force=dist is not None)
     use_graph, graph_note = not args.no_graph, ""
     step_fn = None
@@ -452,6 +485,7 @@ def main():
     from dpc_amd.parallel import gather_step_times, ranks_agree
     dt, rank_ms = gather_step_times(dist, dt, args.steps, dev, world)   # max over ranks; per-rank spread (tests/test_parallel_gloo.py)
     loss = res.cpu().tolist()
+    dumped = dump_outputs(args.dump_outputs, eng, res) if args.dump_outputs and rank == 0 else None   # before any further step
 
     # ---- the other exchange schedules, a few steps each (never part of `value`): the default overlaps the tail all-reduce with
     # layer1 + stem backward and leaves reserve_cus CUs to RCCL; "overlap_all_cus" = the same with every CU claimed by the
@@ -534,6 +568,8 @@ def main():
                        "streams": 2 if getattr(eng, "_side", None) is not None else 1},   # weight gradients beside the next BatchNorm backward
             "final_loss": round(loss[0], 4),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if dist is not None:
             out["per_rank_ms_per_step"] = {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3), "all": [round(v, 3) for v in rank_ms]}
             out["config"]["rccl_knobs"] = rccl_knobs

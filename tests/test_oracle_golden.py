@@ -84,9 +84,11 @@ def test_train_step_p0(golden_dir):
         w = p[n].clone()
         O.adam_step(w, grads[n], torch.zeros_like(w), torch.zeros_like(w), 1)
         # first Adam step moves every element by ~lr*sign(g): an element whose grad is at
-        # the fp32 noise floor may flip sign (2*lr each); allow ~1e-5 of the elements to flip
+        # the fp32 noise floor may flip sign (2*lr each); allow ~1e-5 of the elements to flip, at least one.
+        # The flips come ON TOP of the sum's own rounding noise (rel 1e-5): one flip alone is already the whole 2e-3.
         slack = 2e-3 * max(1.0, 2e-5 * w.numel())
-        assert w.double().sum().item() == pytest.approx(float(g["adam_sum_p0"][i]), rel=1e-5, abs=slack), n
+        e = float(g["adam_sum_p0"][i])
+        assert w.double().sum().item() == pytest.approx(e, rel=0, abs=slack + 1e-5 * abs(e)), n
         if w.numel() >= 8:
             # sign(g)*lr steps: elements whose grad is ~0 may flip; compare with slack of 2*lr
             assert np.abs(w.flatten()[:8].numpy() - g["adam_head_p0"][i]).max() < 2.1e-3, n
