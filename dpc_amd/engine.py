@@ -1020,7 +1020,6 @@ class DPCEngine:
 
     def _backbone_backward(self, d: torch.Tensor, on_tail_ready=None):
         """backward of _backbone_forward from d = d loss / d (last block output); fills the backbone's gradients"""
-        dc = L.dtype_code(self.cdtype)
         carved = False
         for bi in reversed(range(len(self.blocks))):
             if on_tail_ready is not None and bi == self.n_head_blocks - 1:
@@ -1032,6 +1031,11 @@ class DPCEngine:
             d = self.blocks[bi].backward(d, need_dx=True)
         if carved:
             self._carved = True
+        self._stem_backward(d)
+
+    def _stem_backward(self, d: torch.Tensor):
+        """backward of the stem from d = d loss / d (pooled output): fills the gradients of conv1 and bn1"""
+        dc = L.dtype_code(self.cdtype)
         # stem: max-pool routing (ReLU mask folded into the saved argmax) -> BN -> weight grad; the video has no grad
         st = self.stem.out_shape
         u, C0 = self.stem, self.widths[0]

@@ -178,6 +178,180 @@ def basic_block_rounded(x: torch.Tensor, p: Params, pre: str, is3d: bool, stride
     return r(F.relu(out) if final_relu else out)
 
 
+# --------------------------------------------------------------------------
+# the stem: conv1 (1,7,7)/(1,2,2) -> bn1 -> ReLU -> MaxPool3d (1,3,3)/(1,2,2)/(0,1,1) (resnet_2d3d.py:211-214,260-263)
+# --------------------------------------------------------------------------
+STEM_W = "backbone.conv1.weight"
+STEM_G, STEM_B = "backbone.bn1.weight", "backbone.bn1.bias"
+
+
+def pool_by_route(act: torch.Tensor, route: torch.Tensor) -> torch.Tensor:
+    """MaxPool3d((1,3,3),(1,2,2),(0,1,1)) of act [N,C,T,H,W] with the window's tap given instead of searched: route [N,C,T,Ho,Wo]
+    holds kh*3+kw of the chosen tap, 9 = the window passes nothing (the engine's argmax byte).  Differentiable: the gradient goes to
+    the chosen tap only, as max-pool's does to its argmax."""
+    N, Cc, T, H, W = act.shape
+    a = act.permute(0, 2, 1, 3, 4).reshape(N * T, Cc, H, W)
+    win = F.unfold(a, 3, padding=1, stride=2).view(N * T, Cc, 9, -1)
+    win = torch.cat([win, torch.zeros_like(win[:, :, :1])], 2)
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    r = route.permute(0, 2, 1, 3, 4).reshape(N * T, Cc, 1, Ho * Wo).long()
+    out = win.gather(2, r).view(N, T, Cc, Ho, Wo)
+    return out.permute(0, 2, 1, 3, 4)
+
+
+def _stem(x: torch.Tensor, p: Params, r, route: Optional[torch.Tensor]):
+    raw = r(F.conv3d(r(x), r(p[STEM_W]), None, (1, 2, 2), (0, 3, 3)))
+    act = F.relu(bn_batch(raw, p[STEM_G], p[STEM_B]))
+    pooled = F.max_pool3d(act, (1, 3, 3), (1, 2, 2), (0, 1, 1)) if route is None else pool_by_route(act, route)
+    return r(pooled), raw
+
+
+def stem_rounded(x: torch.Tensor, p: Params, route: Optional[torch.Tensor] = None):
+    """the stem with the bf16 engine's storage points: the packed input, the weight, the stored raw conv output and the pooled output
+    pass through ste_round_bf16; BatchNorm statistics are those of the STORED raw values; accumulation stays f32.  x [N,3,T,H,W].
+    Returns (pooled, raw), NCTHW.  route: the pooling taps to use instead of max-pool's own argmax (pool_by_route)."""
+    return _stem(x, p, ste_round_bf16, route)
+
+
+def stem_unrounded(x: torch.Tensor, p: Params, route: Optional[torch.Tensor] = None):
+    """the stem of the f32 engine: stem_rounded without the rounding"""
+    return _stem(x, p, lambda t: t, route)
+
+
+def _ulp(v: torch.Tensor, dtype) -> torch.Tensor:
+    """one unit in the last place of |v| in `dtype` (bf16: 8 significant bits, f32: 24)"""
+    bits = 8 if dtype == torch.bfloat16 else 24
+    _, e = torch.frexp(v.abs().float())
+    return torch.ldexp(torch.ones_like(v, dtype=torch.float32), e - bits)
+
+
+def _taps(t: torch.Tensor, Ho: int, Wo: int):
+    """the nine (kh, kw) views of a [F,C,H+2,W+2] padded tensor under the 3x3 / stride-2 pooling windows, scan order"""
+    return [t[:, :, kh:kh + 2 * Ho - 1:2, kw:kw + 2 * Wo - 1:2] for kh in range(3) for kw in range(3)]
+
+
+def stem_pool_route(pre: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, dtype, floor: torch.Tensor, ulps: float = 1.0):
+    """the max-pool routing of the engine (pool.hip: bn_relu_maxpool_fwd) from the pre-ReLU BatchNorm output pre [F,C,H,W] (frames
+    first): the tap kh*3+kw of the FIRST maximum in scan order among the in-image taps, 9 when that maximum is <= 0 (the ReLU passes
+    no gradient).  pre = raw * scale + shift ([1,C,1,1] each).  Also returns the pooled value, the NEAR-TIE mask -- windows whose two
+    best candidates (the two largest taps, and 0 = no route) lie within `ulps` ulps of the STORED raw value (in `dtype`, mapped through
+    the scale), or within `floor` [C] (the f32 cancellation scale of the channel), where another evaluation of the same stored values
+    may choose the other one -- and each window's first in-image tap.  All [F,C,Ho,Wo]."""
+    Fr, Cc, H, W = pre.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    taps = _taps(F.pad(pre.float(), (1, 1, 1, 1), value=float("-inf")), Ho, Wo)
+    t1 = torch.full((Fr, Cc, Ho, Wo), float("-inf"))
+    t2 = t1.clone()
+    arg = torch.zeros(Fr, Cc, Ho, Wo, dtype=torch.uint8)
+    for k, v in enumerate(taps):
+        upd = v > t1                      # strictly greater: the first maximum stays
+        t2 = torch.where(upd, t1, torch.maximum(t2, v))
+        t1 = torch.where(upd, v, t1)
+        arg.masked_fill_(upd, k)
+    route = torch.where(t1 > 0, arg, torch.full_like(arg, 9))
+    gap = (t1 - t2.clamp_min(0.0)).abs()
+    rmax = torch.maximum(((t1 - shift) / scale).abs(), ((t2 - shift) / scale).abs())   # the stored values of the two best taps
+    near = gap <= torch.maximum(ulps * _ulp(rmax, dtype) * scale.abs(), floor.view(1, Cc, 1, 1))
+    oh = torch.arange(Ho).view(1, 1, Ho, 1)
+    ow = torch.arange(Wo).view(1, 1, 1, Wo)
+    first = ((oh < 1).to(torch.uint8) * 3 + (ow < 1).to(torch.uint8)).expand(Fr, Cc, Ho, Wo)
+    return route, near, t1.clamp_min(0.0), first
+
+
+def route_to_input(dy: torch.Tensor, route: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """the max-pool backward: dy [F,C,Ho,Wo] summed into the taps route [F,C,Ho,Wo] names (9: nowhere) -> [F,C,H,W]"""
+    Fr, Cc, Ho, Wo = dy.shape
+    out = torch.zeros(Fr, Cc, H + 2, W + 2, dtype=dy.dtype)
+    for k, v in enumerate(_taps(out, Ho, Wo)):
+        v += torch.where(route == k, dy, torch.zeros((), dtype=dy.dtype))
+    return out[:, :, 1:H + 1, 1:W + 1]
+
+
+def stem_backward_chunked(x: torch.Tensor, raw: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, dy: torch.Tensor, w_shape,
+                          stored=torch.bfloat16, round_x: bool = True, chunk: int = 64, engine_route: Optional[torch.Tensor] = None,
+                          drop_xhat_term: bool = False, route_first: bool = False, on_chunk=None,
+                          tie_ulps: float = 1.0) -> Dict[str, object]:
+    """closed-form backward of the stem for batches too large for autograd on the CPU, frame chunk by frame chunk, f64 sums.
+
+    x [F,3,H,W] the input frames (frame = clip * T + t, the engine's order); raw [F,Hs,Ws,C] the STORED conv output (its stored dtype,
+    widened one chunk at a time); gamma, beta [C]; dy [F,Ho,Wo,C] the gradient at the pooled output; w_shape the weight's
+    (C,3,1,7,7).  round_x: the input enters the weight gradient bf16-rounded (the engine's packed operand).
+
+    Routing is this function's own (stem_pool_route); engine_route [F,Ho,Wo,C], when given, replaces it on near-tie windows only,
+    and the windows outside those where it disagrees are counted (tie_ulps: the width of a near tie, stem_pool_route).  Mean and invstd come from f64 sums of the stored raw values;
+    dgamma = sum dz_bn * xhat, dbeta = sum dz_bn, and dz = gamma * invstd * (dz_bn - mean(dz_bn) - xhat * mean(dz_bn * xhat)), where
+    dz_bn is dy routed through the pooling; dW = sum over chunks of the f32 weight gradient of the (1,7,7)/(1,2,2)/(0,3,3) conv.
+
+    Mutations, for tests that must show they fail: drop_xhat_term leaves out the mean(dz_bn * xhat) term, route_first sends each
+    routed window's gradient to its first in-image tap instead of its argmax.  on_chunk(f0, f1, d) sees, per chunk, the oracle's
+    pooled output, dz (both [f,C,h,w], f32), its routing and near-tie mask.  Without on_chunk, chunks where dy is zero are not
+    routed, and the near-tie fraction and routing mismatches cover the other chunks only."""
+    Fr, Hs, Ws, Cc = raw.shape
+    n = float(Fr * Hs * Ws)
+    f64 = torch.float64
+    s1 = torch.zeros(Cc, dtype=f64)
+    s2 = torch.zeros(Cc, dtype=f64)
+    for f0 in range(0, Fr, chunk):
+        r = raw[f0:f0 + chunk].to(f64).reshape(-1, Cc)
+        s1 += r.sum(0)
+        s2 += (r * r).sum(0)
+    mean = s1 / n
+    var = (s2 / n - mean * mean).clamp_min(0.0)
+    invstd = 1.0 / torch.sqrt(var + BN_EPS)
+    g64, b64 = gamma.to(f64), beta.to(f64)
+    scale = (g64 * invstd).float().view(1, Cc, 1, 1)
+    shift = (b64 - mean * g64 * invstd).float().view(1, Cc, 1, 1)
+    floor = (1e-6 * (1.0 + b64.abs() + (mean * g64 * invstd).abs())).float()
+    cv = lambda t: t.permute(0, 3, 1, 2)  # channels-last chunk -> [f,C,h,w]
+
+    def routed(f0):
+        rc = cv(raw[f0:f0 + chunk]).float()
+        dyc = cv(dy[f0:f0 + chunk]).float()
+        xhat = (rc.to(f64) - mean.view(1, Cc, 1, 1)) * invstd.view(1, Cc, 1, 1)
+        if on_chunk is None and not bool(dyc.any()):   # no gradient in these frames: nothing to route (nor to count)
+            return torch.zeros_like(rc), xhat, dict(near=torch.zeros((), dtype=torch.bool), mismatch=0)
+        route, near, pooled, first = stem_pool_route(rc * scale + shift, scale, shift, stored, floor, tie_ulps)
+        own = route
+        if engine_route is not None:
+            er = cv(engine_route[f0:f0 + chunk])
+            route = torch.where(near, er, route)
+            bad = int(((er != own) & ~near).sum())
+        else:
+            bad = 0
+        if route_first:
+            route = torch.where(route < 9, first, route)
+        dzb = route_to_input(dyc, route, Hs, Ws)
+        return dzb, xhat, dict(route=route, own_route=own, near=near, pooled=pooled, mismatch=bad)
+
+    # pass 1: the BatchNorm-backward sums
+    dbeta = torch.zeros(Cc, dtype=f64)
+    dgamma = torch.zeros(Cc, dtype=f64)
+    n_near = n_bad = 0
+    for f0 in range(0, Fr, chunk):
+        dzb, xhat, info = routed(f0)
+        dbeta += dzb.to(f64).sum((0, 2, 3))
+        dgamma += (dzb.to(f64) * xhat).sum((0, 2, 3))
+        n_near += int(info["near"].sum())
+        n_bad += info["mismatch"]
+    c1 = (dbeta / n).view(1, Cc, 1, 1)
+    c2 = (dgamma / n).view(1, Cc, 1, 1) if not drop_xhat_term else torch.zeros(1, Cc, 1, 1, dtype=f64)
+    gi = (g64 * invstd).view(1, Cc, 1, 1)
+    # pass 2: dz and the weight gradient
+    dw = torch.zeros(w_shape[0], w_shape[1], w_shape[3], w_shape[4], dtype=f64)
+    for f0 in range(0, Fr, chunk):
+        dzb, xhat, info = routed(f0)
+        dz = (gi * (dzb.to(f64) - c1 - xhat * c2)).float()
+        xc = x[f0:f0 + chunk].float()
+        if round_x:
+            xc = xc.to(torch.bfloat16).float()
+        dw += torch.nn.grad.conv2d_weight(xc, tuple(dw.shape), dz, stride=2, padding=3).to(f64)
+        if on_chunk is not None:
+            on_chunk(f0, min(f0 + chunk, Fr), dict(info, dz=dz))
+    n_win = Fr * Cc * ((Hs - 1) // 2 + 1) * ((Ws - 1) // 2 + 1)
+    return dict(mean=mean, invstd=invstd, dgamma=dgamma, dbeta=dbeta, dw=dw.view(w_shape), near_frac=n_near / n_win,
+                route_mismatch=n_bad)
+
+
 def backbone_forward(p: Params, x: torch.Tensor, network: str = "resnet18") -> torch.Tensor:
     """ResNet2d3d_full.forward (resnet_2d3d.py:259-270); x is [BN,3,T,H,W]."""
     plan = LAYER_PLAN[network]

@@ -276,8 +276,12 @@ def test_bf16_anchored_to_reference(golden_dir, net, size, B, fixture):
         # (their rounding noise acts like a rotation), the engine, which also rounds pooled features, predictions, the recurrence's
         # stored gates and d/dscore, does not.  The norm bound is therefore the larger of the r18 bound, 2x the hooks' own norm noise
         # and HALF of the rel-L2 bound (a norm error can never exceed the rel-L2 error: below that it still says something).
+        # That relaxation is for r34 / 224^2 only: r18 / 128^2 keeps max(ANCHOR_GRADNORM, 2x the hooks' norm noise).
         l2_bound = ANCHOR_NOISE_FACTOR * noise + 0.02
-        assert e_norm < max(ANCHOR_GRADNORM, ANCHOR_NOISE_FACTOR * noise_norm[n], 0.5 * l2_bound), (n, e_norm)
+        norm_bound = max(ANCHOR_GRADNORM, ANCHOR_NOISE_FACTOR * noise_norm[n])
+        if net == "resnet34":
+            norm_bound = max(norm_bound, 0.5 * l2_bound)
+        assert e_norm < norm_bound, (n, e_norm, norm_bound)
         assert e_l2 < l2_bound, (n, e_l2, noise)
 
 
