@@ -1148,6 +1148,11 @@ class DPCEngine:
         """gradients of everything w.r.t. the loss whose d/dscore sits in self.dscore (or is given, [R][R] f32).
         on_tail_ready(flat_g[split:]) is called once every gradient except the stem's and layer1's is final
         (data-parallel runs start their all-reduce there, dpc_amd/parallel.py)."""
+        self._backbone_backward(self._head_backward(dscore_external), on_tail_ready)
+
+    def _head_backward(self, dscore_external: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """backward of the head from d/dscore: score backward -> recurrence -> temporal pool / split, and the ConvGRU / predictor
+        parameter gradients forked onto the side stream.  Returns d_feat, d loss / d (last block output)"""
         B, N, P, SQ, D, M, R = self.B, self.N, self.P, self.SQ, self.D, self.M, self.R
         dc = L.dtype_code(self.cdtype)
         if dscore_external is not None:
@@ -1191,7 +1196,7 @@ class DPCEngine:
         # weight gradients, which queue behind them on the same stream)
         with self.side(site="head"):
             self._head_param_grads(dc)
-        self._backbone_backward(self.d_feat, on_tail_ready)
+        return self.d_feat
 
     def _head_param_grads(self, dc):
         D, M, P, ns = self.D, self.M, self.P, self.n_steps

@@ -389,16 +389,25 @@ def dpc_forward(p: Params, block: torch.Tensor, network: str = "resnet18", pred_
     (num_seq-pred_step)+pred_step pre-scaled masks [B,D,ls,ls] multiplied onto
     the carried hidden state after every GRU step (convrnn.py:78)."""
     B, N, C, SL, H, W = block.shape
-    last_duration, last_size = derived_sizes(H, SL)
-    D = p["network_pred.0.weight"].shape[0]
     feat = backbone_forward(p, block.reshape(B * N, C, SL, H, W), network)
+    assert tuple(feat.shape[2:]) == (derived_sizes(H, SL)[0],) + (derived_sizes(H, SL)[1],) * 2
+    return dpc_head(p, feat, B, pred_step, dropout_masks, return_intermediates)
+
+
+def dpc_head(p: Params, feat: torch.Tensor, B: int, pred_step: int = 3, dropout_masks: Optional[List[torch.Tensor]] = None,
+             return_intermediates: bool = False):
+    """the lines of DPC_RNN.forward after the backbone (dpc/model_3d.py:53-84): feat [B*N,D,T,ls,ls] (the last block's output)
+    -> score [B,P,SQ,B,P,SQ]; dropout_masks as in dpc_forward"""
+    N = feat.shape[0] // B
+    last_duration, last_size = feat.shape[2], feat.shape[3]
+    D = p["network_pred.0.weight"].shape[0]
     feat = F.avg_pool3d(feat, (last_duration, 1, 1), stride=(1, 1, 1))  # model_3d.py:53
     assert feat.shape[2] == 1 and feat.shape[3] == last_size
     feat_inf_all = feat.view(B, N, D, last_size, last_size)
     feature = F.relu(feat).view(B, N, D, last_size, last_size)
     feature_inf = feat_inf_all[:, N - pred_step:].contiguous()  # model_3d.py:58
     k = 0
-    h = torch.zeros(B, D, last_size, last_size, dtype=block.dtype)  # convrnn.py:25-27
+    h = torch.zeros(B, D, last_size, last_size, dtype=feat.dtype)  # convrnn.py:25-27
     for t in range(N - pred_step):  # model_3d.py:62, convrnn.py:76-79
         h = convgru_cell(feature[:, t], h, p)
         if dropout_masks is not None:
@@ -477,6 +486,149 @@ def loss_and_topk(score: torch.Tensor, target: Optional[torch.Tensor] = None):
     correct = pred.t().eq(target.view(1, -1))
     accs = [correct[:k].reshape(-1).float().sum() / rows for k in (1, 3, 5)]
     return loss, accs
+
+
+# --------------------------------------------------------------------------
+# the head with the engine's storage points, on rows m = (b, s) (DPCEngine._build_head / csrc/gru_chain.hip)
+# --------------------------------------------------------------------------
+class _RoundGrad(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        return x.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.float().to(torch.bfloat16).to(g.dtype)
+
+
+def ste_round_grad_bf16(x: torch.Tensor) -> torch.Tensor:
+    """identity in the forward, rounds the GRADIENT to bf16 in the backward: where a bf16 kernel stores a gradient and its
+    consumers read the stored value (the recurrence's gate pre-activation gradients G_all, dP1, dP2)"""
+    return _RoundGrad.apply(x)
+
+
+HEAD_PARAMS = tuple(f"agg.ConvGRUCell_00.{g}.{t}" for g in ("reset_gate", "update_gate", "out_gate") for t in ("weight", "bias")) + \
+    tuple(f"network_pred.{i}.{t}" for i in (0, 2) for t in ("weight", "bias"))
+
+
+def head_rounded(feat: torch.Tensor, params: Params, masks: Optional[torch.Tensor], P: int, rounded: bool = True,
+                 num_seq: Optional[int] = None, pin: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """the head of DPC_RNN.forward (dpc/model_3d.py:53-84, backbone/convrnn.py:24-34) from the engine's saved layer4 output
+    feat [B*N,T,ls,ls,D] (channels-last) to pred and feature_inf [R,D] (rows (b,p,s)), as the engine computes it: the temporal mean,
+    the ReLU / inference split, the recurrence as matrix products on rows (b,s), network_pred.  masks: [n_steps,M,D] pre-scaled keep
+    masks (None: no dropout); num_seq defaults to n_steps + 1 of the masks, else 8.
+
+    rounded: the bf16 engine's storage points pass through ste_round_bf16 (feat_relu / the GRU inputs, feature_inf, the state after
+    dropout, h*r, relu(W1 h + b1), pred, relu(pred) as the next input, the packed GRU / predictor weights), and the gradients the
+    backward kernel stores in bf16 and reuses through ste_round_grad_bf16 (the gate pre-activation gradients, dP1, dP2).  Biases,
+    gates and accumulation stay in the input's precision.  Returns pred, feat_inf, feat_relu [N,M,D], X_all, H_all (h_0 first),
+    HR_all, P1_all: tensors of the graph (differentiable).
+
+    pin: the engine's STORED values of those tensors (same names and layouts; any subset).  A pinned storage point takes the stored
+    value in the forward and passes the gradient through unchanged: the backward is then differentiated at the engine's own saved
+    operands, as its kernels are, and bf16 rounding flips of the forward (another accumulation order) no longer feed the backward."""
+    r = ste_round_bf16 if rounded else (lambda t: t)
+    rg = ste_round_grad_bf16 if rounded else (lambda t: t)
+    BN, T, ls, ls2, D = feat.shape
+    N = num_seq if num_seq is not None else (masks.shape[0] + 1 if masks is not None else 8)
+    B, SQ = BN // N, ls * ls2
+    M, n_agg = B * SQ, N - P
+    pin = pin or {}
+
+    def rs(t, name, idx=None):   # a storage point: rounded, or the engine's stored value
+        if name not in pin:
+            return r(t)
+        v = pin[name] if idx is None else pin[name][idx]
+        return t + (v.to(t.dtype).reshape(t.shape) - t).detach()
+
+    pred_rows = lambda i: pin["pred"].reshape(B, P, SQ, D)[:, i] if "pred" in pin else None
+    mean = feat.mean(1).reshape(B, N, SQ, D)                                      # model_3d.py:53
+    feat_inf = rs(mean[:, N - P:], "feat_inf").reshape(B * P * SQ, D)             # model_3d.py:58, pre-ReLU
+    feat_relu = r(F.relu(mean)).permute(1, 0, 2, 3).reshape(N, M, D)             # [n][(b,s)][d]
+    pre = "agg.ConvGRUCell_00."
+    W = {g: r(params[pre + g + "_gate.weight"].reshape(D, 2 * D)) for g in ("update", "reset", "out")}
+    Bs = {g: params[pre + g + "_gate.bias"] for g in ("update", "reset", "out")}
+    W1, W2 = r(params["network_pred.0.weight"].reshape(D, D)), r(params["network_pred.2.weight"].reshape(D, D))
+    b1, b2 = params["network_pred.0.bias"], params["network_pred.2.bias"]
+
+    def cell(x, h):   # convrnn.py:24-34 with kernel_size 1: the convolutions are products on rows
+        c = torch.cat([x, h], 1)
+        u = torch.sigmoid(rg(c @ W["update"].t() + Bs["update"]))
+        rr = torch.sigmoid(rg(c @ W["reset"].t() + Bs["reset"]))
+        hr = rs(h * rr, "HR_all", k)
+        o = torch.tanh(rg(torch.cat([x, hr], 1) @ W["out"].t() + Bs["out"]))
+        return h * (1 - u) + o * u, hr
+
+    h = torch.zeros(M, D, dtype=feat.dtype)
+    X, H, HR, P1, preds = [], [h], [], [], []
+    k = 0
+
+    def step(x, h):
+        nonlocal k
+        x = rs(x, "X_all", k) if "X_all" in pin else x
+        hn, hr = cell(x, h)
+        X.append(x)
+        HR.append(hr)
+        h = rs(hn * masks[k] if masks is not None else hn, "H_all", k + 1)
+        k += 1
+        H.append(h)
+        return h
+
+    for t in range(n_agg):                                                        # model_3d.py:62
+        h = step(feat_relu[t], h)
+    for i in range(P):                                                            # model_3d.py:66-71
+        p1 = rs(F.relu(rg(h @ W1.t() + b1)), "P1_all", i)
+        P1.append(p1)
+        p2 = rg(p1 @ W2.t() + b2)
+        preds.append(r(p2) if "pred" not in pin else p2 + (pred_rows(i).reshape(M, D).to(p2.dtype) - p2).detach())
+        if i < P - 1:   # the state after the last prediction is never used
+            h = step(r(F.relu(p2)), h)
+    pred = torch.stack(preds, 0).reshape(P, B, SQ, D).permute(1, 0, 2, 3).reshape(B * P * SQ, D)
+    return dict(pred=pred, feat_inf=feat_inf, feat_relu=feat_relu, X_all=torch.stack(X), H_all=torch.stack(H),
+                HR_all=torch.stack(HR), P1_all=torch.stack(P1))
+
+
+def _to_bf16(t: torch.Tensor) -> torch.Tensor:
+    """t rounded the way an f32 kernel value is stored in bf16 (through f32: no double rounding against the engine)"""
+    return t.float().to(torch.bfloat16).to(t.dtype)
+
+
+def score_ce_backward_chunked(pred: torch.Tensor, finf: torch.Tensor, logits: str = "f32", round_ds: bool = True,
+                              chunk: int = 1024) -> Dict[str, torch.Tensor]:
+    """score = pred @ finf^T (dpc/model_3d.py:83), CrossEntropyLoss with target = arange (main.py:213-217) and its backward in closed
+    form, in f64, row chunk by row chunk (the [R][R] score never exists at once: 1.9 GB of f64 at R = 15 680).  pred, finf [R,D].
+
+    logits "bf16": the logits are rounded to bf16 before the softmax and the rank (the train step's score16); round_ds: d/dscore =
+    (softmax - onehot) / R is rounded to bf16 before both products, as the bf16 engine stores (or, fused, recomputes) it.  Returns the
+    loss, per-row loss terms, the per-row rank (logits STRICTLY greater than the target's: ties rank behind), the
+    top-1/3/5 accuracies, d_pred = dS @ finf and d_finf = dS^T @ pred."""
+    if logits not in ("f32", "bf16"):
+        raise ValueError("logits must be 'f32' or 'bf16'")
+    R, D = pred.shape
+    p64, f64 = pred.double(), finf.double()
+    terms = torch.empty(R, dtype=torch.float64)
+    rank = torch.empty(R, dtype=torch.int64)
+    d_pred = torch.empty(R, D, dtype=torch.float64)
+    d_finf = torch.zeros(R, D, dtype=torch.float64)
+    for i0 in range(0, R, chunk):
+        i1 = min(i0 + chunk, R)
+        rows = torch.arange(i1 - i0)
+        S = p64[i0:i1] @ f64.t()
+        if logits == "bf16":
+            S = _to_bf16(S)
+        tgt = S[rows, rows + i0]
+        lse = torch.logsumexp(S, 1)
+        terms[i0:i1] = lse - tgt
+        rank[i0:i1] = (S > tgt[:, None]).sum(1)
+        dS = torch.exp(S - lse[:, None])
+        dS[rows, rows + i0] -= 1.0
+        dS /= R
+        if round_ds:
+            dS = _to_bf16(dS)
+        d_pred[i0:i1] = dS @ f64
+        d_finf += dS.t() @ p64[i0:i1]
+    accs = [(rank < kk).double().mean().item() for kk in (1, 3, 5)]
+    return dict(loss=terms.mean(), terms=terms, rank=rank, accs=accs, d_pred=d_pred, d_finf=d_finf)
 
 
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int,

@@ -438,3 +438,16 @@ def test_module_copies_and_no_grad(emu):
     assert not torch.equal(next(c.parameters()), next(m.parameters()))
     with pytest.raises(TypeError, match="state_dict"):
         pickle.dumps(m)
+
+
+@pytest.mark.parametrize("dtype,score_path,materialise", [(torch.float32, "auto", True), (torch.bfloat16, "auto", True),
+                                                          (torch.bfloat16, "fused", False)])
+def test_head_backward_vs_rounding_oracle(emu, dtype, score_path, materialise):
+    """DPCEngine._head_backward (score backward, recurrence, temporal pool / split, parameter gradients) against oracle.head_rounded +
+    score_ce_backward_chunked: the wiring and indexing of tests/test_head_grads_gpu.py at D = 32, where the loader / compute GEMMs are
+    not selected (they need N % 128)"""
+    import head_cases as hc
+    e = hc.engine("resnet18", 64, 3, 2, dtype, score_path, device="cpu", widths=WIDTHS, lib=emu)
+    assert e._tn_splits is None
+    hc.case(e, f"simulator D={e.D} {str(dtype)[6:]} {score_path}", materialise, mutate=materialise)
+    assert e.score_mode == ("fused" if score_path == "fused" else "materialised")
