@@ -13,7 +13,12 @@ Timing: ``value`` comes from K steps with NO instrumentation (barrier + synchron
 over ranks).  The roofline objects come from a second, separately instrumented pass (HIP events around
 the selected C-ABI launches on the launch stream) that does not touch ``value``.
 
-Prints ONE JSON line on rank 0, including
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs if
+asked, print the line.  Everything else it can measure (the instrumented pass with its live PMC traffic, the
+`also` side measurements, the CPU baseline) runs after the timed steps with ``--full`` only; ``--no-roofline``,
+``--no-also`` and ``--no-cpu-baseline`` leave single parts of it out.
+
+Prints ONE JSON line on rank 0, including (with --full)
   roofline     -- the dominant kernel family (implicit-GEMM conv, MFMA-bound): algorithmic FLOPs per
                   launch / average launch duration
   score_gemm   -- the contrastive score contraction (forward + both backward GEMMs), the metric's named
@@ -383,10 +388,13 @@ def main():
     ap.add_argument("--pred_step", type=int, default=None)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "bf16x6"],
                     help="f32 = the parity mode (1e-3 vs the reference); bf16x6 = f32 tensors with the contractions on the bf16 matrix pipe (parity-grade)")
-    ap.add_argument("--roofline-steps", type=int, default=4, help="steps of the separately instrumented pass")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the 224^2 side measurements (cfg4 / cfg5) of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the instrumented roofline pass (live PMC traffic), "
+                         "the `also` side measurements of the default cfg2 line and the CPU baseline.  Off: the line carries the timed steps only")
+    ap.add_argument("--roofline-steps", type=int, default=4, help="steps of the separately instrumented pass (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the instrumented pass")
+    ap.add_argument("--no-also", action="store_true", help="--full without the side measurements (cfg4 / cfg5 / ...) of the default run")
     ap.add_argument("--schedules", action="store_true",
                     help="multi-rank runs: after the timed region also time the other gradient-exchange schedules (two more captures with other "
                          "collectives; opt-in: a side measurement must not be able to cost a scaling run its line)")
@@ -396,7 +404,7 @@ def main():
                     "captured into the graph): +0.3 ms per step at cfg2.  Default: ONE resident synthetic block, re-used by every step "
                     "(config.input says which)")
     ap.add_argument("--pmc", default="auto", choices=["auto", "live", "file", "off"],
-                    help="roofline.traffic: live = two rocprofv3 --pmc passes of a child run (default at cfg2 / bf16 / one GPU: 'auto' tries it and "
+                    help="roofline.traffic (--full): live = two rocprofv3 --pmc passes of a child run (default at cfg2 / bf16 / one GPU: 'auto' tries it and "
                          "falls back to the tracked profiles/*_pmc_traffic.json, flagged); file = the tracked profile only; off = null")
     ap.add_argument("--score-path", default="auto", choices=["auto", "fused", "materialised"],
                     help="contrastive score + loss: fused (no [R][R] tensor in HBM) or materialised; auto = materialised (the faster one at cfg2 and at cfg5)")
@@ -541,7 +549,7 @@ def main():
 
     # ---- separately instrumented pass (never part of `value`): HIP events around the selected launches
     timer = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         timer = KernelTimer(["dpc_conv_igemm", "dpc_conv_igemm_ex", "dpc_conv_wgrad", "dpc_score_fwd", "dpc_score_bwd", "dpc_gemm_nt_splitk", "dpc_gemm_tn_splitk",
                              "dpc_reduce_unpack"] + list(HBM_FAMILY))
         eng.timer = timer
@@ -639,7 +647,7 @@ def main():
                     "frac": round(by / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "ms_per_step": round(ms / rs, 3),
                     "algorithmic_GB_per_step": round(by / rs / 1e9, 3), "launches_per_step": sum(d["launches"] for d in hb) // rs,
                 }
-        if world == 1 and dist is None and args.config == "cfg2" and args.batch is None and args.dtype == "bf16" and not args.no_also:
+        if args.full and world == 1 and dist is None and args.config == "cfg2" and args.batch is None and args.dtype == "bf16" and not args.no_also:
             del eng, step_fn, block
             torch.cuda.empty_cache()
             out["also"] = {}
@@ -654,7 +662,7 @@ def main():
                     torch.cuda.synchronize()
             if "value" in out["also"].get("module", {}):
                 out["also"]["module"]["vs_engine_path"] = round(out["also"]["module"]["value"] / out["value"], 3)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     if dist is not None:
         dist.barrier()

@@ -18,7 +18,7 @@ reach autograd as fresh views of the gradient arena, which AccumulateGrad adopts
 ``.grad``, and ``dpc_amd.optim.Adam`` is the fused arena update behind
 ``torch.optim.Optimizer``'s interface.  ``model.bfloat16()`` / ``model.float()`` (or
 ``DPC_COMPUTE_DTYPE=bf16``) select the kernels' operand type; parameters stay f32.
-bench.py times the reference's own loop lines over this module (``also.module``).
+``bench.py --full`` times the reference's own loop lines over this module (``also.module``).
 """
 from __future__ import annotations
 
