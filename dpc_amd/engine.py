@@ -617,6 +617,8 @@ class DPCEngine:
         BN, H = batch * num_seq, sample_size
         dt = self.cdtype
         self.x_s2d = self.empty((BN, seq_len, H // 2, H // 2, 16), dt)
+        # synthetic-input draw counter (fill_synthetic): advanced in front of every draw, read by dpc_synthetic_input on the device
+        self.dev_input = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.stem = _ConvBN(self, "backbone.conv1.weight", "backbone.bn1", 16, widths[0], (1, 4, 4), (1, 1, 1), (0, 2, 2),
                             (BN, seq_len, H // 2, H // 2), stem=True)
         hp = (H // 2 - 1) // 2 + 1
@@ -999,6 +1001,17 @@ class DPCEngine:
         from .data import recipe_to_input
         recipe_to_input(self.lib, frames, starts, clips, self.N, self.SL, ds, self.size, None, self.x_s2d)
 
+    def fill_synthetic(self, seed: int, block: Optional[torch.Tensor] = None):
+        """a new synthetic N(0,1) batch drawn on the device (csrc/synthetic.hip): advances dev_input, then writes the stem's operand
+        (and `block` [B,N,3,SL,H,W] f32 with the same values when given).  Follow with forward(None, ...) / train_step(None, ...).
+        Graph-safe: captured in front of a step (capture_train_step / capture_eval_step refill=) it draws a new batch per replay."""
+        if block is not None and (tuple(block.shape) != (self.B, self.N, 3, self.SL, self.size, self.size) or block.dtype != torch.float32
+                                  or not block.is_contiguous() or block.device != self.device):
+            raise ValueError(f"block must be a contiguous float32 {(self.B, self.N, 3, self.SL, self.size, self.size)} on {self.device}")
+        self.call("dpc_counter_advance", self.dev_input)
+        self.call("dpc_synthetic_input", block, self.x_s2d, L.dtype_code(self.cdtype), self.B * self.N, self.SL, self.size, self.size,
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, self.dev_input)
+
     def _backbone_forward(self, block: Optional[torch.Tensor]) -> torch.Tensor:
         """2d3d-ResNet (backbone/resnet_2d3d.py:259-270) on block [B,N,3,SL,H,W] (None: the stem operand was filled by
         load_frames): returns the last block's output [B*N, T, ls, ls, D] (channels-last, no final ReLU)"""
@@ -1247,21 +1260,28 @@ class DPCEngine:
         gd = getattr(self, "gru_desc", None)
         return (float(self.lr), float(self.wd), float(gd.p_drop) if gd is not None else 0.0, int(gd.seed) if gd is not None else 0)
 
-    def capture_train_step(self, block: torch.Tensor, allreduce=None, warmup: int = 2, refill=None):
+    def check_graph_capture(self):
+        """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
+        if self.device.type != "cuda":
+            raise L.DpcError("hipGraph capture needs the HIP device")
+
+    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
         """Captures the whole train step on `block` (a static device buffer: refill it in place between replays) into
         hipGraphs and returns ``replay() -> device f32[4]``.  One graph without data parallelism; with the two-bucket
         gradient exchange the capture is cut where the backward hands the gradient tail to RCCL, so the replay is
         graph A (forward, loss, backward down to layer2) -> all-reduce(tail) asynchronously -> graph B (layer1 + stem
         backward) -> all-reduce(head) + join -> graph C (Adam).  Dropout masks and Adam's bias corrections are keyed on
-        the device-side step counter, so every replay is a new optimizer step."""
-        if self.device.type != "cuda":
-            raise L.DpcError("hipGraph capture needs the HIP device")
+        the device-side step counter, so every replay is a new optimizer step.
+        block=None: the step starts from the stem's operand as it stands (train_step(None)): filled in the graph by
+        ``refill=lambda: eng.fill_synthetic(seed)``, or eagerly before each replay (load_recipe)."""
+        self.check_graph_capture()
         # every host scalar the capture bakes into kernel arguments is part of the key (dpc_adam_dev takes lr / wd by value, the
         # recurrence descriptor p_drop / seed): after eng.lr = ... (LR schedule, checkpoint.resume, --reset_lr) asking again captures
         # a step with the new values instead of handing back the stale replay (ADVICE r5)
         # refill: optional callable captured in FRONT of the step (e.g. ``lambda: block.normal_()``: a fresh synthetic batch per replay
         # from torch's graph-safe default generator -- SURVEY section 8d "generated ON DEVICE"); part of the key by identity
-        key = (block.data_ptr(), tuple(block.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
+        buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
+        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
                id(refill) if refill is not None else None) + self._baked_scalars()
         hit = self._captures.get(key)
         if hit is not None:   # the same static buffer, the same exchange: the capture that exists (see _LIVE_GRAPHS)
@@ -1313,6 +1333,7 @@ class DPCEngine:
                 graphs.append(state["g"])
         finally:
             events, self._capture_events = self._capture_events, None
+        self.packed_for_step = -1   # the capture executed nothing: the packed weights are not those of this step yet
         cur.wait_stream(side)
         tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:self.grad_split], self.flat_g, self.result
         me = weakref.ref(self)   # the cached closure must not keep its engine (tens of GB of buffers) alive through a cycle
@@ -1340,7 +1361,62 @@ class DPCEngine:
 
         replay.graphs = graphs
         replay.events = events   # destroyed after the graphs, not before
-        replay.block = block   # the static input buffer stays alive (and its address un-reused) as long as the capture does
+        replay.block = buf   # the static input buffer stays alive (and its address un-reused) as long as the capture does
+        replay.refill = refill
+        self._captures[key] = replay
+        self._capture_graphs.append(_Capture(graphs, events))
+        return replay
+
+    def capture_eval_step(self, refill=None):
+        """Captures one validation step on the stem's operand -- `refill` (e.g. ``lambda: eng.fill_synthetic(seed)``), then
+        forward(None, train=False, materialise=False) + loss_topk(with_grad=False) -- into one hipGraph and returns
+        ``replay() -> device f32[4]``.  The weight repack is inside the graph unconditionally, so a replay after more training
+        evaluates the weights of now, not those of the capture.  Same rules as capture_train_step: the baked host scalars are part
+        of the cache key, the graph is parked (_LIVE_GRAPHS), never destroyed while the process runs.  No eager warm-up: run one
+        eager validation step first (the forward allocates its ReLU masks on first use)."""
+        self.check_graph_capture()
+        key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
+        hit = self._captures.get(key)
+        if hit is not None:
+            return hit
+        if self._pack_table is None:
+            self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
+        cur = torch.cuda.current_stream(self.device)
+        side = torch.cuda.Stream(self.device)
+        torch.cuda.synchronize(self.device)
+        side.wait_stream(cur)
+        g = torch.cuda.CUDAGraph()
+        keep_events = os.environ.get("DPC_KEEP_CAPTURE_EVENTS", "1") != "0"   # (see capture_train_step)
+        self._capture_events = [] if keep_events else None
+        try:
+            with torch.cuda.stream(side):
+                g.capture_begin(pool=torch.cuda.graph_pool_handle())
+                self.packed_for_step = -1
+                if refill is not None:
+                    refill()
+                self.forward(None, train=False, materialise=False)
+                self.loss_topk(with_grad=False)
+                g.capture_end()
+        finally:
+            events, self._capture_events = self._capture_events, None
+        self.packed_for_step = -1   # the capture executed nothing
+        cur.wait_stream(side)
+        graphs, result = [g], self.result
+        me = weakref.ref(self)
+        baked = self._baked_scalars()
+
+        def replay():
+            eng = me()
+            if eng is None:
+                raise RuntimeError("replay of a captured evaluation step whose engine is gone")
+            if eng._baked_scalars() != baked:
+                raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
+                                   "call capture_eval_step() again")
+            graphs[0].replay()
+            return result
+
+        replay.graphs = graphs
+        replay.events = events
         replay.refill = refill
         self._captures[key] = replay
         self._capture_graphs.append(_Capture(graphs, events))

@@ -11,6 +11,8 @@ are averaged with one RCCL all-reduce (dpc_amd/parallel.py).  Datasets / augment
 epoch with the dataset's tensor layout [B, num_seq, 3, seq_len, H, W] (dpc/dataset_3d.py:109-111), or -- ``--frames clips.npy`` --
 decoded uint8 frames [clips, F, H0, W0, 3] on which the training transform of ``--dataset`` (dpc/main.py:114-132) runs on the GPU
 (dpc_amd/data.py FrameSource -> engine.load_recipe -> train_step(None): SURVEY.md §8 f4).
+``--graph`` runs every step after a short eager warm-up as a replay of one captured train step and one captured validation step
+(DESIGN.md §9.5.1); the synthetic input is then drawn on the device inside the graph (engine.fill_synthetic) instead of by torch.randn.
 Checkpoints are the reference's dictionary (``module.``-prefixed state_dict incl. alias keys, torch-Adam-layout
 ``optimizer``; dpc/main.py:166-174, utils/utils.py:14-26) written and read by ``dpc_amd/checkpoint.py``: a file
 written here resumes in the reference and vice versa (tests/test_checkpoint.py).
@@ -56,6 +58,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--val_frames', default='', type=str, help='frames for validate() (default: the --frames array; the reference validates '
                         'with the training transform too, dpc/main.py:135-136)')
     parser.add_argument('--crop', default=224, type=int, help='RandomCrop size of the ucf101 recipe (dpc/main.py:117)')
+    parser.add_argument('--graph', action='store_true', help='train and validate on replayed hipGraph steps: the first two train steps and '
+                        'the first validation step of the run are eager (warm-up), every later step replays one captured step, and rank 0 '
+                        'prints the replayed steps\' ms/step after each training epoch.  Synthetic input is then drawn on the device inside '
+                        'the graph (engine.fill_synthetic, seed 1000 + rank) instead of by torch.randn: the batches differ from a run '
+                        'without --graph.  --frames input is unchanged: the same draws and bit-identical results.  HIP device only')
     return parser
 
 
@@ -133,6 +140,8 @@ def _worker(rank: int, world: int, args, port: int):
     widths = getattr(args, '_widths', None) or LAYER_WIDTH
     eng = DPCEngine(args.net, args.img_dim, args.num_seq, args.seq_len, args.pred_step, per_gpu, dev, cdt, widths, lib=sim, lr=args.lr, wd=args.wd,
                     seed=233 + rank, reserve_cus=default_reserve_cus(world))  # dropout stream: the reference seeds 233 (dpc/model_3d.py:18); independent per replica
+    if args.graph:
+        eng.check_graph_capture()   # before the first step: --graph never falls back to kernel-by-kernel launches
     init = DPC_RNN(args.img_dim, args.num_seq, args.seq_len, args.pred_step, args.net, widths=widths, seed=0)  # same on every rank
     eng.load_params({k: v.detach() for k, v in init.named_parameters()})
     best_acc, iteration = 0.0, 0
@@ -170,21 +179,44 @@ def _worker(rank: int, world: int, args, port: int):
         src_train = mk(args.frames)
         src_val = mk(args.val_frames) if args.val_frames else src_train
 
+    # --graph: per run, the first `warm[train]` steps of each kind run eagerly, then ONE captured step per kind is replayed.  Synthetic
+    # input: `refill` draws the batch on the device in front of the step (inside the graph once captured); --frames: load_recipe fills
+    # the operand eagerly before each step and the graph starts from it
+    warm, captured = {True: 2, False: 1}, {True: None, False: None}
+    refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
+
     def run_epoch(train: bool, epoch: int):
         losses, accs = AverageMeter(), [AverageMeter() for _ in range(3)]
         nonlocal iteration
         src = src_train if train else src_val
         n_batches = len(src) if src is not None else args.synthetic
         feed = src.epoch(dev) if src is not None else None
+        replayed, ev0, ev1 = 0, None, None
         for idx in range(n_batches):
             tic = time.time()
+            block = None
             if feed is not None:
                 frames, starts, clips = next(feed)
                 eng.load_recipe(frames, starts, clips, ds=src.ds)   # fills the stem's operand; no f32 video in between
-                block = None
-            else:
+            elif not args.graph:
                 block = torch.randn(shape, device=dev, generator=gen)
-            if train:
+            replay = args.graph and warm[train] == 0
+            if args.graph and not replay:   # eager warm-up step
+                warm[train] -= 1
+                if refill is not None:
+                    refill()
+            if replay:
+                if captured[train] is None:
+                    captured[train] = (eng.capture_train_step(None, allreduce=allreduce, warmup=0, refill=refill) if train
+                                       else eng.capture_eval_step(refill))
+                if train and ev0 is None:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                res = captured[train]()
+                if train:
+                    ev1.record()
+                    replayed += 1
+            elif train:
                 res = eng.train_step(block, allreduce=allreduce)
             else:  # validate(): dropout off, BN still batch statistics (dpc/main.py:249-282, model_3d.py:28)
                 eng.forward(block, train=False, materialise=False)  # loss / top-k only: the score is never written (bf16)
@@ -200,6 +232,11 @@ def _worker(rank: int, world: int, args, port: int):
                         epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic), flush=True)
                 if train:
                     iteration += 1
+        if replayed:   # device time from the first replayed train step of the epoch to the end of its last one
+            ev1.synchronize()
+            ms = ev0.elapsed_time(ev1) / replayed
+            if rank == 0:
+                print('Graph replay: {0} steps, {1:.3f} ms/step, {2:.1f} clips/s'.format(replayed, ms, args.batch_size * 1e3 / ms), flush=True)
         return losses.local_avg, accs[0].local_avg, [a.local_avg for a in accs]
 
     for epoch in range(args.start_epoch, args.epochs):

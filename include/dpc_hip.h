@@ -186,6 +186,14 @@ int dpc_transpose2d(const void* in, int32_t dtype_in, int32_t ld_in, void* out, 
  * dpc_pack_stem_weight: [Co][3][1][7][7] f32 -> [Co][16 taps][16]; dpc_unpack_stem_wgrad the inverse for grads. */
 int dpc_pack_input_s2d(const float* block, void* out, int32_t dtype_out, int32_t BN, int32_t T, int32_t H, int32_t W,
                        dpc_stream_t stream);
+/* dpc_synthetic_input: one N(0,1) batch drawn on the device, written to block [BN][3][T][H][W] f32 and / or straight into the
+ *   stem operand out [BN][T][H/2][W/2][16] (exactly what dpc_pack_input_s2d writes from that block); either pointer may be NULL.
+ *   Element e of the block, q = e >> 2: (w0..w3) = Philox4x32-10(counter (q, draw_dev[0], 2 = DPC_PHILOX_STREAM_INPUT, 0),
+ *   key (lo(seed), hi(seed))); for j in {0,1}: u = ((w_2j >> 8) + 1) 2^-24, v = (w_2j+1 >> 8) 2^-24, r = sqrtf(-2 logf(u)),
+ *   th = 6.2831855f v, x[4q+2j] = r cosf(th), x[4q+2j+1] = r sinf(th).  The draw counter is read on the device, never written:
+ *   dpc_counter_advance in front of it gives every replay of a captured step a new batch. */
+int dpc_synthetic_input(float* block, void* out, int32_t dtype_out, int32_t BN, int32_t T, int32_t H, int32_t W, uint64_t seed,
+                        const int32_t* draw_dev, dpc_stream_t stream);
 int dpc_pack_stem_weight(const float* w, void* out, int32_t dtype_out, int32_t Co, dpc_stream_t stream);
 int dpc_unpack_stem_wgrad(const float* part, int32_t nsplit, float* dw, int32_t Co, dpc_stream_t stream);
 
