@@ -143,6 +143,10 @@ _SIGS = {
                             C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
     "dpc_frames_to_input_ex": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(Resample), _vp, _vp, _vp,
                                C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
+    "dpc_video_windows_to_input": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(Resample),
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
+    "dpc_lc_test_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "dpc_lc_test_finish": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_stem_wgrad_fused": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "dpc_adam": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
 }

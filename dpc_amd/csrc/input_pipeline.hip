@@ -19,6 +19,8 @@
 //                    -- verified against PIL for all 2^24 colours on the host (tests/golden/make_aug_golden.py)
 //   ToTensor (/255) + Normalize(mean, std)                                                        (augmentation.py:368-379)
 //   stack / view / transpose to [N, C, SL, H, W]                                                  (dataset_3d.py:107-111)
+//   test-time windows  dpc_video_windows_to_input: ONE resident video, clip b = the window that starts at aug[b].start
+//                    (eval/dataset_3d_lc.py:109-127: every frame at stride ds, seq_len blocks, a sliding num_seq window)
 // written either as the boundary tensor block [B][N][3][SL][H][W] f32 (what DPC_RNN.forward takes) or DIRECTLY as the
 // stem's space-to-depth operand (dpc_pack_input_s2d's output), so that a host-fed step moves 1/4 of the bytes over PCIe
 // (uint8 instead of f32) and the f32 video never exists in HBM.
@@ -35,6 +37,7 @@ constexpr int RS_PREC = 32 - 8 - 2;  // PIL ImagingResample PRECISION_BITS
 struct Geo {
     const uint8_t* frames;
     int B, F, H0, W0;
+    int clip_pitch;  // frames between clip b and clip b + 1: F, or 0 when every clip reads the same video (test-time windows)
     const dpc_clip_aug* aug;
     const int8_t* gray;
     int N, SL, ds, H, W;
@@ -51,7 +54,7 @@ __device__ __forceinline__ int clip8(int v) {
 
 // the three channels of output pixel (y, x) of frame (b, f): crop / flip / resize, then the RandomGray channel choice
 __device__ __forceinline__ void geo_pixel(const Geo& g, int b, int f, int gch, const dpc_clip_aug& a, int y, int x, int (&rgb)[3]) {
-    const uint8_t* fr = g.frames + ((long long)b * g.F + f) * g.H0 * g.W0 * 3;
+    const uint8_t* fr = g.frames + ((long long)b * g.clip_pitch + f) * g.H0 * g.W0 * 3;
     // flip = 1: flip AFTER crop (+ resize) (the k400 recipe); flip = 2: flip of the full frame BEFORE the crop (ucf101)
     const int xo = a.flip == 1 ? g.W - 1 - x : x;
     if (g.xb) {
@@ -300,7 +303,7 @@ extern "C" int dpc_frames_to_input(const uint8_t* frames, int32_t B, int32_t F, 
     if (!xtab != !ytab) return DPC_ERR_ARG;
     if (!xtab) { crop_w = W; crop_h = H; }
     if (crop_h > H0 || crop_w > W0 || crop_w <= 0 || crop_h <= 0) return DPC_ERR_UNSUPPORTED;
-    Geo g = {frames, B, F, H0, W0, aug, gray, N, SL, ds, H, W, xtab, ytab, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    Geo g = {frames, B, F, H0, W0, F, aug, gray, N, SL, ds, H, W, xtab, ytab, nullptr, nullptr, nullptr, nullptr, 0, 0};
     const unsigned grid = grid_cells((long long)B * N * SL * (H / 2) * (W / 2));
     if (!s2d || dtype_s2d == DPC_F32) {
         DPC_LAUNCH((frames_geo_kernel<float, false>), dim3(grid), dim3(256), stream, g, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], block,
@@ -323,7 +326,7 @@ extern "C" int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t 
     if (jitter && (!u8_ws || !lsum_ws)) return DPC_ERR_ARG;
     if (rs && (!rs->xb || !rs->xk || !rs->yb || !rs->yk || rs->ksx <= 0 || rs->ksy <= 0)) return DPC_ERR_ARG;
     if (s2d && dtype_s2d != DPC_F32 && dtype_s2d != DPC_BF16) return DPC_ERR_ARG;
-    Geo g = {frames, B, F, H0, W0, aug, gray, N, SL, ds, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    Geo g = {frames, B, F, H0, W0, F, aug, gray, N, SL, ds, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     if (rs) { g.xb = rs->xb; g.xk = rs->xk; g.yb = rs->yb; g.yk = rs->yk; g.ksx = rs->ksx; g.ksy = rs->ksy; }
     const long long cells = (long long)B * N * SL * (H / 2) * (W / 2);
     const unsigned grid = grid_cells(cells);
@@ -346,6 +349,33 @@ extern "C" int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t 
     } else {
         DPC_LAUNCH((frames_jitter_kernel<float>), dim3(grid), dim3(256), stream, (const uint8_t*)u8_ws, jitter, (const unsigned long long*)lsum_ws, B, N, SL, H, W,
                    mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], block, (float*)s2d);
+    }
+    return dpc_launch_status();
+}
+
+// The test protocol of eval/dataset_3d_lc.py:109-127 without replicating frames: `video` is ONE video [F][H0][W0][3] that every
+// clip of the batch reads, clip b = the window whose first frame is aug[b].start (frame(n, sl) = start + (n * SL + sl) * ds as
+// above).  dpc_frames_to_input_ex without gray / jitter and with a clip pitch of 0 in the frame address.  The caller validates
+// start + (N * SL - 1) * ds < F and the resampling windows on the host (dpc_amd/data.py: video_windows_to_input).
+extern "C" int dpc_video_windows_to_input(const uint8_t* video, int32_t B, int32_t F, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                                          int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
+                                          const float* mean3, const float* std3, float* block, void* s2d, int32_t dtype_s2d,
+                                          dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_common(video, B, F, H0, W0, aug, N, SL, ds, H, W, mean3, std3, block, s2d)) return rc;
+    if ((long long)(N * SL - 1) * ds >= F) return DPC_ERR_ARG;
+    if (rs && (!rs->xb || !rs->xk || !rs->yb || !rs->yk || rs->ksx <= 0 || rs->ksy <= 0)) return DPC_ERR_ARG;
+    if (!rs && (H > H0 || W > W0)) return DPC_ERR_ARG;
+    if (s2d && dtype_s2d != DPC_F32 && dtype_s2d != DPC_BF16) return DPC_ERR_ARG;
+    Geo g = {video, B, F, H0, W0, 0, aug, nullptr, N, SL, ds, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+    if (rs) { g.xb = rs->xb; g.xk = rs->xk; g.yb = rs->yb; g.yk = rs->yk; g.ksx = rs->ksx; g.ksy = rs->ksy; }
+    const unsigned grid = grid_cells((long long)B * N * SL * (H / 2) * (W / 2));
+    if (s2d && dtype_s2d == DPC_BF16) {
+        DPC_LAUNCH((frames_geo_kernel<bf16_t, false>), dim3(grid), dim3(256), stream, g, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], block,
+                   (bf16_t*)s2d, (uint8_t*)nullptr);
+    } else {
+        DPC_LAUNCH((frames_geo_kernel<float, false>), dim3(grid), dim3(256), stream, g, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], block,
+                   (float*)s2d, (uint8_t*)nullptr);
     }
     return dpc_launch_status();
 }

@@ -133,44 +133,51 @@ def _tables_from_index(idx: np.ndarray):
     return b, np.full((len(idx), 1), 1 << RS_PREC, np.int32)
 
 
-def _draw_gray_and_jitter(n_frames: int, gray_p: float, jitter: Optional[dict]):
-    """RandomGray(consistent=False, p) then ColorJitter(..., consistent=False, p) over the frames of one clip, call for call
-    (utils/augmentation.py:229-243 and :310-351)"""
+def _jitter_get_params(j: FrameJitter, jitter: dict):
+    """ColorJitter.get_params (utils/augmentation.py:298-326) into one dpc_frame_jitter: four uniform draws, then random.shuffle of the list"""
+    ops: List[int] = []
+    for op, name in enumerate(("brightness", "contrast", "saturation", "hue")):
+        v = jitter.get(name, 0)
+        if not v:
+            continue
+        lo, hi = (-v, v) if name == "hue" else (max(0.0, 1.0 - v), 1.0 + v)   # _check_input
+        f = random.uniform(lo, hi)
+        if name == "hue":
+            j.hue_shift = int(f * 255) & 0xFF   # np.uint8(hue_factor * 255): C truncation, uint8 wrap
+        else:
+            j.factor[op] = f
+        ops.append(op)
+    random.shuffle(ops)
+    for k, op in enumerate(ops):
+        j.order[k] = op
+
+
+def _draw_gray_and_jitter(n_frames: int, gray_p: float, jitter: Optional[dict], consistent: bool = False):
+    """RandomGray(consistent=False, p) then ColorJitter(..., p) over the frames of one clip, call for call (utils/augmentation.py:229-243
+    and :310-351).  consistent=False: one get_params draw per frame (the pre-training recipes); consistent=True: ONE draw copied to
+    every frame (:330-333, the fine-tuning recipes of eval/test.py:161-176).  gray_p = None: the recipe has no RandomGray."""
     gray = np.full(n_frames, -1, np.int8)
-    for i in range(n_frames):                       # RandomGray: one Bernoulli per frame, then np.random.choice(3)
-        if random.random() < gray_p:
-            gray[i] = np.random.choice(3)
+    if gray_p is not None:
+        for i in range(n_frames):                   # RandomGray: one Bernoulli per frame, then np.random.choice(3)
+            if random.random() < gray_p:
+                gray[i] = np.random.choice(3)
     jit = (FrameJitter * n_frames)()
     for i in range(n_frames):
         jit[i].order[:] = [255, 255, 255, 255]
     if jitter is not None and random.random() < jitter.get("p", 1.0):
-        for i in range(n_frames):                   # get_params per frame: four uniform draws, then random.shuffle of the list
-            ops: List[int] = []
-            for op, name in enumerate(("brightness", "contrast", "saturation", "hue")):
-                v = jitter.get(name, 0)
-                if not v:
-                    continue
-                lo, hi = (-v, v) if name == "hue" else (max(0.0, 1.0 - v), 1.0 + v)   # _check_input
-                f = random.uniform(lo, hi)
-                if name == "hue":
-                    jit[i].hue_shift = int(f * 255) & 0xFF   # np.uint8(hue_factor * 255): C truncation, uint8 wrap
-                else:
-                    jit[i].factor[op] = f
-                ops.append(op)
-            random.shuffle(ops)
-            for k, op in enumerate(ops):
-                jit[i].order[k] = op
+        for i in range(1 if consistent else n_frames):
+            _jitter_get_params(jit[i], jitter)
+        if consistent:
+            for i in range(1, n_frames):
+                jit[i] = jit[0]
     return gray, jit
 
 
-def draw_k400(W0: int, H0: int, size: int, n_frames: int, gray_p: float = 0.5,
-              jitter: Optional[dict] = dict(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.25, p=1.0)):
-    """the k400 training recipe (dpc/main.py:124-132) for ONE clip of n_frames frames of W0 x H0 pixels:
-    RandomSizedCrop(size, consistent=True, p=1.0) -> RandomHorizontalFlip(consistent=True) -> RandomGray(p=0.5) -> ColorJitter.
-    Consumes `random` / `np.random` exactly as the reference's classes do.  Returns dict(x1, y1, flip, xb, xk, yb, yk, gray, jitter)."""
-    x1 = y1 = 0
-    xt = yt = None
-    if random.random() < 1.0:                                   # RandomSizedCrop.threshold = p = 1.0
+def _draw_sized_crop(W0: int, H0: int, size: int, p: float):
+    """RandomSizedCrop(size, BILINEAR, consistent=True, p).__call__ (utils/augmentation.py:151-195) on W0 x H0 frames: the crop box and the
+    BILINEAR resize to size x size as resampling tables.  Returns (x1, y1, (xb, xk), (yb, yk), taken); taken = False is the CenterCrop(size)
+    branch of a failed `p` draw (:193-195), an index map."""
+    if random.random() < p:                                     # RandomSizedCrop.threshold = p
         for _ in range(10):
             area = W0 * H0
             target_area = random.uniform(0.5, 1) * area
@@ -182,15 +189,26 @@ def draw_k400(W0: int, H0: int, size: int, n_frames: int, gray_p: float = 0.5,
             if w <= W0 and h <= H0:
                 x1 = random.randint(0, W0 - w)
                 y1 = random.randint(0, H0 - h)
-                xt, yt = resample_tables(w, size), resample_tables(h, size)
-                break
-        else:   # fallback (augmentation.py:190-193): Scale(size) then CenterCrop(size), both on the whole frame
-            if W0 < H0:
-                ow, oh = size, int(size * H0 / W0)
-            else:
-                oh, ow = size, int(size * W0 / H0)
-            cx, cy = int(round((ow - size) / 2.)), int(round((oh - size) / 2.))
-            xt, yt = resample_tables(W0, ow, cx, size), resample_tables(H0, oh, cy, size)
+                return x1, y1, resample_tables(w, size), resample_tables(h, size), True
+        # fallback (augmentation.py:190-193): Scale(size) then CenterCrop(size), both on the whole frame
+        if W0 < H0:
+            ow, oh = size, int(size * H0 / W0)
+        else:
+            oh, ow = size, int(size * W0 / H0)
+        cx, cy = int(round((ow - size) / 2.)), int(round((oh - size) / 2.))
+        return 0, 0, resample_tables(W0, ow, cx, size), resample_tables(H0, oh, cy, size), True
+    if W0 < size or H0 < size:
+        raise ValueError(f"CenterCrop({size}) of {W0} x {H0} frames leaves the frame (PIL would pad with black; not reproduced)")
+    ident = np.arange(size, dtype=np.int32)
+    return int(round((W0 - size) / 2.)), int(round((H0 - size) / 2.)), _tables_from_index(ident), _tables_from_index(ident), False
+
+
+def draw_k400(W0: int, H0: int, size: int, n_frames: int, gray_p: float = 0.5,
+              jitter: Optional[dict] = dict(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.25, p=1.0)):
+    """the k400 training recipe (dpc/main.py:124-132) for ONE clip of n_frames frames of W0 x H0 pixels:
+    RandomSizedCrop(size, consistent=True, p=1.0) -> RandomHorizontalFlip(consistent=True) -> RandomGray(p=0.5) -> ColorJitter.
+    Consumes `random` / `np.random` exactly as the reference's classes do.  Returns dict(x1, y1, flip, xb, xk, yb, yk, gray, jitter)."""
+    x1, y1, xt, yt, _ = _draw_sized_crop(W0, H0, size, 1.0)
     flip = 1 if random.random() < 0.5 else 0                    # RandomHorizontalFlip(consistent=True): after the crop + resize
     gray, jit = _draw_gray_and_jitter(n_frames, gray_p, jitter)
     return dict(x1=x1, y1=y1, flip=flip, xb=xt[0], xk=xt[1], yb=yt[0], yk=yt[1], gray=gray, jitter=jit)
@@ -209,6 +227,76 @@ def draw_ucf101(W0: int, H0: int, crop: int, size: int, n_frames: int, gray_p: f
     xb, xk = _tables_from_index(idx)
     gray, jit = _draw_gray_and_jitter(n_frames, gray_p, jitter)
     return dict(x1=x1, y1=y1, flip=flip, xb=xb, xk=xk, yb=xb.copy(), yk=xk.copy(), gray=gray, jitter=jit)
+
+
+LC_RECIPES = {   # eval/test.py:161-176 (train, val) and :121-126 (test): RandomSizedCrop's p, flip, ColorJitter(consistent=True)
+    "train": dict(p=1.0, flip=True, jitter=dict(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.25, p=0.3)),
+    "val": dict(p=0.3, flip=True, jitter=dict(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.1, p=0.3)),
+    "test": dict(p=0.0, flip=False, jitter=None),
+}
+
+
+def draw_lc(W0: int, H0: int, crop: int = 224, size: int = 128, n_frames: int = 40, mode: str = "train"):
+    """the three recipes of the downstream classifier (eval/test.py:121-126,161-176) for ONE clip: RandomSizedCrop(size=crop, BILINEAR,
+    consistent=True, p) -> Scale((size, size)) [NEAREST] -> RandomHorizontalFlip(consistent=True) -> ColorJitter(consistent=True, p=0.3);
+    the test recipe has neither flip nor jitter and p = 0.0 (always the CenterCrop).  Same `random` calls in the same order as the
+    reference's classes; same contract as draw_k400.  The NEAREST Scale after the BILINEAR resize picks rows of the BILINEAR table:
+    PIL's resize is separable and per output sample, so a sub-sampled output is an exact subset."""
+    if mode not in LC_RECIPES:
+        raise ValueError(f"mode must be one of {sorted(LC_RECIPES)}")
+    r = LC_RECIPES[mode]
+    x1, y1, xt, yt, taken = _draw_sized_crop(W0, H0, crop, r["p"])
+    idx = nearest_tables(crop, size) if crop != size else np.arange(size, dtype=np.int32)
+    flip = (1 if random.random() < 0.5 else 0) if r["flip"] else 0   # after crop + scale
+    gray, jit = _draw_gray_and_jitter(n_frames, None, r["jitter"], consistent=True)
+    return dict(x1=x1, y1=y1, flip=flip, xb=xt[0][idx], xk=xt[1][idx], yb=yt[0][idx], yk=yt[1][idx], gray=gray, jitter=jit, sized_crop=taken)
+
+
+def lc_test_windows(vlen: int, num_seq: int, seq_len: int, ds: int, dataset: str = "ucf101") -> List[int]:
+    """first frames of the test-time windows of one video (eval/dataset_3d_lc.py:72-78,109-127): every frame at stride ds, cut into
+    seq_len blocks, a num_seq-block window slid by num_seq // 2 blocks (ucf101, :124) or 3 * num_seq // 4 (hmdb51, :254).  A video with
+    vlen - num_seq * seq_len * ds <= 0 has no window: the dataset class drops it (:61-67)."""
+    if dataset not in ("ucf101", "hmdb51"):
+        raise ValueError("dataset not supported")
+    stride = num_seq // 2 if dataset == "ucf101" else 3 * num_seq // 4
+    if num_seq < 2 or stride < 1:
+        raise ValueError(f"num_seq {num_seq}: the window stride of the test protocol is {stride} blocks (range() with step 0 in the reference)")
+    if vlen - num_seq * seq_len * ds <= 0:
+        return []
+    nblk = len(range(0, vlen, ds)) // seq_len
+    return [w * seq_len * ds for w in range(0, nblk + 1 - num_seq, stride)]
+
+
+def video_windows_to_input(lib: L.Lib, video: torch.Tensor, vlen: int, starts, clip: dict, num_seq: int, seq_len: int, ds: int, size: int,
+                           block: Optional[torch.Tensor] = None, s2d: Optional[torch.Tensor] = None):
+    """ONE video u8 [F,H0,W0,3] on the kernels' device, of which the first vlen frames are real; starts[b] = first frame of window b
+    (lc_test_windows); clip = one draw_lc(..., mode='test') result, shared by the windows (the transform sees the whole video once,
+    dataset_3d_lc.py:96).  Fills block f32 [B,N,3,SL,size,size] and / or the stem's operand through dpc_video_windows_to_input:
+    no frame is replicated."""
+    if video.dim() != 4 or video.shape[3] != 3 or video.dtype != torch.uint8:
+        raise ValueError("video must be uint8 [F,H0,W0,3]")
+    F, H0, W0, _ = video.shape
+    B, n_fr = len(starts), num_seq * seq_len
+    if not 0 < vlen <= F:
+        raise ValueError(f"a video of {F} frames cannot have length {vlen}")
+    for b, st in enumerate(starts):   # the kernel trusts these
+        if st < 0 or st + (n_fr - 1) * ds >= vlen:
+            raise ValueError(f"window {b}: frames {st} .. {st + (n_fr - 1) * ds} do not fit a video of {vlen} frames")
+    c = clip
+    if c["x1"] < 0 or c["y1"] < 0 or c["x1"] + int((c["xb"][:, 0] + c["xb"][:, 1]).max()) > W0 or \
+            c["y1"] + int((c["yb"][:, 0] + c["yb"][:, 1]).max()) > H0:
+        raise ValueError(f"the crop box / resampling window leaves the {W0} x {H0} frame")
+    if any(j.order[0] != 255 for j in c["jitter"]) or (np.asarray(c["gray"]) >= 0).any():
+        raise ValueError("the windowed gather has no gray / jitter stage (the test recipe draws none)")
+    dev = video.device
+    aug = np.array([(st, c["x1"], c["y1"], c["flip"]) for st in starts], np.int32)
+    rep = lambda a: torch.from_numpy(np.repeat(a[None].astype(np.int32), B, 0)).to(dev)   # noqa: E731  (the kernel indexes its tables by clip)
+    t = dict(aug=torch.from_numpy(aug).to(dev), xb=rep(c["xb"]), xk=rep(c["xk"]), yb=rep(c["yb"]), yk=rep(c["yk"]))
+    rs = L.Resample(t["xb"].data_ptr(), t["xk"].data_ptr(), t["yb"].data_ptr(), t["yk"].data_ptr(), c["xk"].shape[1], c["yk"].shape[1])
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    lib.call("dpc_video_windows_to_input", video.contiguous(), B, F, H0, W0, t["aug"], num_seq, seq_len, ds, size, size, C.byref(rs),
+             mean, std, block, s2d, L.dtype_code(s2d.dtype) if s2d is not None else L.F32, lib.stream())
+    return block, s2d
 
 
 def recipe_to_input(lib: L.Lib, frames: torch.Tensor, starts, clips: "List[dict]", num_seq: int, seq_len: int, ds: int, size: int,
@@ -304,3 +392,71 @@ class FrameSource:
                 clips.append(draw_k400(W0, H0, self.size, self.n_fr) if self.dataset == "k400"
                              else draw_ucf101(W0, H0, self.crop, self.size, self.n_fr))
             yield torch.from_numpy(host).to(device, non_blocking=False), [0] * self.batch, clips
+
+
+class LabelledFrameSource:
+    """Labelled videos for ``python -m dpc_amd.lc_main --frames``: frames uint8 [clips, F, H0, W0, 3], labels integer [clips] (0-based
+    class ids), optional lengths integer [clips] (the real frame count of each video, <= F; default F).  It stands where the
+    reference has ``UCF101_3d`` / ``HMDB51_3d`` (eval/dataset_3d_lc.py) under its DataLoaders (eval/test.py:345-380): for
+    'train' / 'val' a random permutation cut into batches (drop_last), per clip the start frame of ``idx_sampler``
+    (``np.random.choice(range(vlen - num_seq * seq_len * ds))``, :79) and then the draws of ``draw_lc``; for the test protocol
+    ``videos()`` walks the file in order.  Videos too short for one clip are dropped, as the dataset classes do (:61-67)."""
+
+    def __init__(self, frames, labels, dataset: str, num_seq: int, seq_len: int, ds: int, size: int, batch: int, num_class: int,
+                 recipe: str = "train", lengths=None, rank: int = 0, world: int = 1, crop: int = 224):
+        self.frames = np.load(frames, mmap_mode="r") if isinstance(frames, (str, bytes)) or hasattr(frames, "__fspath__") else frames
+        fr = self.frames
+        if fr.ndim != 5 or fr.shape[4] != 3 or fr.dtype != np.uint8:
+            raise ValueError("--frames wants a uint8 array [clips, F, H0, W0, 3]")
+        if dataset not in ("ucf101", "hmdb51"):
+            raise ValueError("dataset not supported")   # eval/test.py:378
+        if recipe not in LC_RECIPES:
+            raise ValueError(f"recipe must be one of {sorted(LC_RECIPES)}")
+        load = lambda a: np.load(a) if isinstance(a, (str, bytes)) or hasattr(a, "__fspath__") else np.asarray(a)  # noqa: E731
+        labels = load(labels)
+        lengths = np.full(fr.shape[0], fr.shape[1], np.int64) if lengths is None else load(lengths)
+        for name, a in (("labels", labels), ("lengths", lengths)):
+            if a.ndim != 1 or a.shape[0] != fr.shape[0] or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"--{name} wants one integer per clip: {fr.shape[0]} clips, array of shape {a.shape} and type {a.dtype}")
+        if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= num_class):
+            raise ValueError(f"labels must lie in [0, {num_class}): found {int(labels.min())} .. {int(labels.max())}")
+        if lengths.size and (int(lengths.min()) < 0 or int(lengths.max()) > fr.shape[1]):
+            raise ValueError(f"lengths must lie in [0, {fr.shape[1]}] (the frames the array holds): found {int(lengths.min())} .. {int(lengths.max())}")
+        if fr.shape[2] < crop or fr.shape[3] < crop:
+            raise ValueError(f"the recipes crop {crop} x {crop} (eval/test.py:122,162,170): frames of {fr.shape[3]} x {fr.shape[2]} are too small")
+        self.labels, self.lengths = labels.astype(np.int64), lengths.astype(np.int64)
+        self.dataset, self.N, self.SL, self.ds, self.size, self.batch = dataset, num_seq, seq_len, ds, size, batch
+        self.rank, self.world, self.crop, self.recipe, self.num_class = rank, world, crop, recipe, num_class
+        self.n_fr = num_seq * seq_len
+        self.span = (self.n_fr - 1) * ds + 1
+        self.keep = [i for i in range(fr.shape[0]) if int(self.lengths[i]) - self.n_fr * ds > 0]
+        self.skipped = fr.shape[0] - len(self.keep)
+
+    def __len__(self):   # batches per epoch, drop_last
+        return len(self.keep) // (self.batch * self.world)
+
+    def epoch(self, device):
+        """yields (frames u8 [B, span, H0, W0, 3] on `device`, starts (all 0: the span is cut out on the host), clips, labels int64 [B])
+        per batch of THIS rank"""
+        fr = self.frames
+        H0, W0 = fr.shape[2:4]
+        order = [self.keep[i] for i in torch.randperm(len(self.keep)).tolist()]     # RandomSampler
+        gb = self.batch * self.world
+        for i in range(len(self)):
+            mine = order[i * gb + self.rank * self.batch: i * gb + (self.rank + 1) * self.batch]
+            clips, host = [], np.empty((self.batch, self.span, H0, W0, 3), np.uint8)
+            for j, ci in enumerate(mine):
+                start = int(np.random.choice(range(int(self.lengths[ci]) - self.n_fr * self.ds), 1)[0])         # idx_sampler
+                host[j] = fr[ci, start:start + self.span]
+                clips.append(draw_lc(W0, H0, self.crop, self.size, self.n_fr, self.recipe))
+            yield torch.from_numpy(host).to(device, non_blocking=False), [0] * self.batch, clips, torch.from_numpy(self.labels[mine])
+
+    def videos(self):
+        """the test protocol, in file order: (index, frames u8 [vlen, H0, W0, 3] host array, label, window starts, the test recipe's
+        draw) for every video long enough (``skipped`` counts the others)"""
+        fr = self.frames
+        H0, W0 = fr.shape[2:4]
+        for ci in self.keep:
+            vlen = int(self.lengths[ci])
+            starts = lc_test_windows(vlen, self.N, self.SL, self.ds, self.dataset)
+            yield ci, fr[ci, :vlen], int(self.labels[ci]), starts, draw_lc(W0, H0, self.crop, self.size, self.n_fr, "test")

@@ -220,6 +220,49 @@ class LCEngine(DPCEngine):
         self.adam_step()
         return self.result
 
+    # ---- the video-level test of eval/test.py:303-343 (csrc/lc_test.hip): per-video state, run totals and the confusion matrix on the device
+    def test_reset(self):
+        """zero the run totals (sum loss, sum top-1, sum top-5, videos), the confusion matrix [pred][target] and the per-video state"""
+        NC, f32 = self.num_class, torch.float32
+        z = lambda *shape, dt=f32: torch.zeros(*shape, dtype=dt, device=self.device)   # noqa: E731
+        self.test_psum, self.test_lsum, self.test_count = z(NC), z(NC), z(1, dt=torch.int32)
+        self.test_prob, self.test_res = z(NC), z(4)
+        self.test_totals, self.test_confusion = z(4, dt=torch.float64), z(NC, NC, dt=torch.int64)
+        self.test_label = torch.zeros(self.B, dtype=torch.int64)
+
+    def test_video(self, frames_u8, label: int, starts, clip: dict, ds: int = 3, vlen: Optional[int] = None):
+        """one video of the test protocol: frames_u8 uint8 [vlen, H0, W0, 3] (host array or tensor; uploaded ONCE), its class label,
+        the window start frames (data.lc_test_windows) and the test recipe's draw (data.draw_lc(..., 'test')).  Per chunk of B windows:
+        gather into the stem's operand (dpc_video_windows_to_input) -> eval-mode forward -> dpc_lc_test_accumulate with the chunk's
+        valid count; the last chunk is padded by repeating its last window (finite rows; eval-mode BatchNorm uses running statistics,
+        so rows do not see each other) and its padding rows are never summed.  Then dpc_lc_test_finish.  Nothing crosses to the
+        host: ``test_res`` (loss, top-1, top-5, pred), ``test_prob`` (mean probability) hold this video, ``test_totals`` /
+        ``test_confusion`` the run (``test_reset`` starts one)."""
+        from .data import video_windows_to_input
+        if not hasattr(self, "test_totals"):
+            self.test_reset()
+        label = int(label)
+        if not 0 <= label < self.num_class:
+            raise ValueError(f"label {label} is outside [0, {self.num_class})")
+        starts = [int(s) for s in starts]
+        if not starts:
+            raise ValueError("a video without windows is skipped by the caller (data.lc_test_windows returned none)")
+        video = frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.from_numpy(frames_u8.copy() if hasattr(frames_u8, "copy") else frames_u8)
+        video = video.to(self.device)
+        vlen = video.shape[0] if vlen is None else int(vlen)
+        B = self.B
+        self.test_label.fill_(label)
+        for i in range(0, len(starts), B):
+            st = starts[i:i + B]
+            n_valid = len(st)
+            st = st + [st[-1]] * (B - n_valid)
+            video_windows_to_input(self.lib, video, vlen, st, clip, self.N, self.SL, ds, self.size, None, self.x_s2d)
+            self.forward(None, self.test_label, train=False)
+            self.call("dpc_lc_test_accumulate", self.logits, B, n_valid, self.num_class, self.num_class, self.test_psum, self.test_lsum,
+                      self.test_count)
+        self.call("dpc_lc_test_finish", self.test_psum, self.test_lsum, self.test_count, self.num_class, label, self.test_prob, self.test_res,
+                  self.test_totals, self.test_confusion)
+
     # the DPC-specific entry points do not exist on this engine
     def loss_topk(self, with_grad: bool = True):
         return self.result

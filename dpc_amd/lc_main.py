@@ -3,8 +3,23 @@
     python -m dpc_amd.lc_main --net resnet18 --img_dim 128 --batch_size 128 --gpu 0 --pretrain <dpc checkpoint> --synthetic 20
 
 train() / validate() / test() follow eval/test.py:218-343 on the LCEngine (one process per GPU, RCCL gradient
-all-reduce as in dpc_amd.main); datasets, augmentation and tensorboard are outside this build's scope, the input is
-synthetic N(0,1) video with random labels in the dataset's tensor layout.  ``--pretrain`` loads a DPC-RNN checkpoint
+all-reduce as in dpc_amd.main).  Data: without ``--frames`` the input is synthetic N(0,1) video with random labels in the
+dataset's tensor layout; with
+
+    python -m dpc_amd.lc_main --frames videos.npy --labels labels.npy [--lengths lengths.npy] --pretrain <dpc checkpoint> --save_dir out
+    python -m dpc_amd.lc_main --frames videos.npy --labels labels.npy [--lengths lengths.npy] --test out/epoch10.pth.tar --gpu 0
+
+it is decoded uint8 frames [clips, F, H0, W0, 3] with integer labels [clips] (and the real frame count of each video, <= F):
+fine-tuning and validation run the train / val transforms of eval/test.py:161-176 on the GPU (dpc_amd/data.py: draw_lc,
+LabelledFrameSource -> engine.load_recipe -> train_step(None, labels)); ``--test`` runs the reference's video-level protocol
+(eval/test.py:303-343 + eval/dataset_3d_lc.py:72-127): every frame at stride ``--ds`` cut into ``seq_len`` blocks, a
+``num_seq``-block window slid with half overlap (3/4 for hmdb51), all windows through the model in eval mode from ONE uploaded
+copy of the video (csrc/input_pipeline.hip: dpc_video_windows_to_input), softmax averaged over the windows for top-1 / top-5,
+logits averaged for the loss and the confusion matrix -- reduced on the device (csrc/lc_test.hip), read back once after the last
+video.  It prints the reference's result line, writes ``<ckpt>.confusion.npy`` (int64 [num_class, num_class], [pred][target])
+where the reference draws ``<ckpt>.svg`` and appends the reference's paragraph to ``test_log.md`` beside the checkpoint.  Video
+decoding, csv split files and tensorboard stay outside this build's scope: whatever produces these arrays plugs in.
+``--pretrain`` loads a DPC-RNN checkpoint
 by key intersection (neq_load_customized, backbone/resnet_2d3d.py:310-333): backbone + ConvGRU weights are taken, the
 running buffers and the head stay at their initial values -- exactly what the reference does with its own checkpoints.
 
@@ -20,6 +35,7 @@ from __future__ import annotations
 
 import argparse
 import os
+import time
 
 import torch
 
@@ -50,10 +66,29 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--prefix', default='tmp', type=str)
     parser.add_argument('--img_dim', default=128, type=int)
     # additions of this build
-    parser.add_argument('--synthetic', default=20, type=int, help='synthetic batches per epoch (the only data source here)')
+    parser.add_argument('--synthetic', default=20, type=int, help='synthetic batches per epoch (the data source unless --frames is given)')
     parser.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
     parser.add_argument('--save_dir', default='', type=str)
+    parser.add_argument('--frames', default='', type=str, help='uint8 .npy [clips, F, H0, W0, 3] of decoded frames: the transforms of '
+                        'eval/test.py:121-126,161-176 run on the GPU (dpc_amd/data.py); replaces --synthetic.  With --test: the video-level '
+                        'test protocol over the videos in file order')
+    parser.add_argument('--labels', default='', type=str, help='integer .npy [clips] of 0-based class ids (required with --frames)')
+    parser.add_argument('--lengths', default='', type=str, help='integer .npy [clips]: the real frame count of each video, <= F (default: F)')
+    parser.add_argument('--val_frames', default='', type=str, help='frames for validate() (default: the --frames array.  The reference '
+                        'validates on a 30 %% pandas sample of its TEST split, eval/dataset_3d_lc.py:44-46,69: a property of its csv files, not '
+                        'of this build -- pass that sample here)')
+    parser.add_argument('--val_labels', default='', type=str, help='labels of --val_frames')
+    parser.add_argument('--val_lengths', default='', type=str, help='lengths of --val_frames')
+    parser.add_argument('--crop', default=224, type=int, help='side of RandomSizedCrop / CenterCrop in the recipes (eval/test.py:122,162,170)')
     return parser
+
+
+def write_log(content: str, epoch: int, filename: str):
+    """utils/utils.py:160-168"""
+    with open(filename, 'a') as f:
+        f.write('## Epoch %d:\n' % epoch)
+        f.write('time: %s\n' % str(time.strftime('%Y_%m_%d_%H_%M_%S', time.localtime())))
+        f.write(content + '\n\n')
 
 
 def lr_multiplier(epoch: int, gamma: float, milestones, repeat: int) -> float:
@@ -140,6 +175,45 @@ def _worker(rank: int, world: int, args, port: int):
             if not args.reset_lr and 'optimizer' in ck:
                 ckpt.load_optimizer_state(eng, ck['optimizer'])  # restores the group's lr as optimizer.load_state_dict does
     allreduce = make_allreduce(dist, world)
+    probe = getattr(args, '_probe', None)   # tests only: the rank leaves its arenas (and in test mode the totals) behind
+    src_train = src_val = None
+    if args.frames:   # labelled uint8 frames in (eval/dataset_3d_lc.py + the transforms of eval/test.py:121-126,161-176 on the GPU)
+        import random
+        import numpy as np
+        from .data import LabelledFrameSource
+        if not args.labels:
+            raise ValueError('--frames needs --labels')
+        if bool(args.val_frames) != bool(args.val_labels):
+            raise ValueError('--val_frames and --val_labels come together')
+        torch.manual_seed(0)      # the epoch permutation (RandomSampler): the same on every rank, each takes its shard
+        random.seed(rank)
+        np.random.seed(rank)      # as dpc_amd.main: one stream per rank like one per loader worker (eval/test.py seeds nothing)
+        mk = lambda fr, lb, ln, recipe: LabelledFrameSource(fr, lb, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu,  # noqa: E731
+                                                            args.num_class, recipe, ln or None, rank, world, args.crop)
+        if args.test:
+            src_test = mk(args.frames, args.labels, args.lengths, 'test')
+            t0 = time.time()
+            eng.test_reset()
+            for _, frames, label, starts, clip in src_test.videos():
+                eng.test_video(frames, label, starts, clip, ds=args.ds)
+            loss_sum, top1, top5, n_vid = eng.test_totals.cpu().tolist()   # the ONE readback of the run (+ the confusion matrix below)
+            confusion = eng.test_confusion.cpu()
+            n = max(n_vid, 1.0)
+            line = 'Loss {:.4f}\t Acc top1: {:.4f} Acc top5: {:.4f} \t'.format(loss_sum / n, top1 / n, top5 / n)
+            log(line)
+            log('(test checkpoint epoch {})'.format(num_epoch))
+            log('{} videos tested, {} skipped (too short for {} x {} frames at stride {}), {:.1f} s'.format(
+                int(n_vid), src_test.skipped, args.num_seq, args.seq_len, args.ds, time.time() - t0))
+            if args.test != 'random':   # where the reference writes <ckpt>.svg and test_log.md (eval/test.py:338-341)
+                np.save(args.test + '.confusion.npy', confusion.numpy())
+                write_log(content=line, epoch=num_epoch, filename=os.path.join(os.path.dirname(args.test), 'test_log.md'))
+            if probe:
+                torch.save({'totals': [loss_sum, top1, top5, n_vid], 'confusion': confusion, 'skipped': src_test.skipped,
+                            'flat_p': eng.flat_p.detach().cpu(), 'flat_m': eng.flat_m.detach().cpu(), 'step': eng.step_count},
+                           os.path.join(probe, f'rank{rank}.pt'))
+            return
+        src_train = mk(args.frames, args.labels, args.lengths, 'train')
+        src_val = mk(args.val_frames, args.val_labels, args.val_lengths, 'val') if args.val_frames else mk(args.frames, args.labels, args.lengths, 'val')
     gen = torch.Generator(dev).manual_seed(1000 + rank)
     shape = (per_gpu, args.num_seq, 3, args.seq_len, args.img_dim, args.img_dim)
 
@@ -169,22 +243,36 @@ def _worker(rank: int, world: int, args, port: int):
         log('(test checkpoint epoch {})'.format(num_epoch))
     else:
         for epoch in range(args.start_epoch, args.epochs):
-            for idx in range(args.synthetic):  # train(): eval/test.py:218-271
-                x, y = batch()
+            n_train = len(src_train) if src_train is not None else args.synthetic
+            feed = src_train.epoch(dev) if src_train is not None else None
+            for idx in range(n_train):  # train(): eval/test.py:218-271
+                if feed is not None:
+                    frames, starts, clips, y = next(feed)
+                    eng.load_recipe(frames, starts, clips, ds=args.ds)   # fills the stem's operand; no f32 video in between
+                    x = None
+                else:
+                    x, y = batch()
                 res = eng.train_step(x, y, allreduce=allreduce)
                 if idx % args.print_freq == 0:
                     loss, acc = reduce(res)
-                    log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, args.synthetic, loss, acc, eng.lr),
+                    log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr),
                         flush=True)
                     iteration += 1  # advanced on logged steps only, as the reference does (eval/test.py:262-270)
             vl = va = 0.0
-            for idx in range(max(args.synthetic // 4, 1)):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
-                x, y = batch()
+            n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
+            feed = src_val.epoch(dev) if src_val is not None else None
+            for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
+                if feed is not None:
+                    frames, starts, clips, y = next(feed)
+                    eng.load_recipe(frames, starts, clips, ds=args.ds)
+                    x = None
+                else:
+                    x, y = batch()
                 eng.forward(x, y, train=False)
                 loss, acc = reduce(eng.result)
                 vl += loss
                 va += acc
-            nv = max(args.synthetic // 4, 1)
+            nv = max(n_val, 1)
             val_acc = va / nv
             log('Loss {:.4f}\t Acc: {:.4f} \t'.format(vl / nv, val_acc), flush=True)
             eng.lr = base_lr * lr_multiplier(epoch, 0.1, milestones, 1)  # scheduler.step(epoch), eval/test.py:197
@@ -196,16 +284,21 @@ def _worker(rank: int, world: int, args, port: int):
                          'best_acc': best_acc, 'optimizer': ckpt.optimizer_state_dict(eng), 'iteration': iteration}
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
         log('Training from ep %d to ep %d finished' % (args.start_epoch, args.epochs))
+        if probe:
+            torch.save({'flat_p': eng.flat_p.detach().cpu(), 'flat_m': eng.flat_m.detach().cpu(), 'step': eng.step_count, 'rank': rank,
+                        'world': world, 'per_gpu': per_gpu}, os.path.join(probe, f'rank{rank}.pt'))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
 
 
-def main(argv=None, _simulator=None, _widths=None):
+def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
-    args._simulator, args._widths = _simulator, _widths   # tests/test_entries.py: the CPU tier runs the entry on the simulator
+    args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     gpus = [g for g in str(args.gpu).split(',') if g != '']
     world = max(len(gpus), 1)
+    if args.test and args.frames and world != 1:   # the reference's DataParallel over the windows of a video is not reproduced
+        raise ValueError('--test with --frames runs on one GPU (the windows of a video are chunked on it): pass --gpu 0')
     if _simulator is not None and world != 1:
         raise ValueError('the simulator runs one rank')
     if world == 1:

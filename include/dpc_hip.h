@@ -442,6 +442,28 @@ int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t F, int32_t 
                            const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3, const float* std3,
                            float* block, void* s2d, int32_t dtype_s2d, dpc_stream_t stream);
 
+/* The test-time windows of eval/dataset_3d_lc.py:109-127 from ONE resident video: `video` u8 [F][H0][W0][3] is read by every clip
+ * of the batch, clip b = the window whose first frame is aug[b].start (aug[b].flip as above; the test transform never flips).
+ * dpc_frames_to_input_ex without gray / jitter; rs [B] tables as there (NULL = plain crop of H x W at (x1, y1)).  The caller has
+ * checked aug[b].start + (N*SL - 1)*ds < F and the crop box / resampling windows against the frame. */
+int dpc_video_windows_to_input(const uint8_t* video, int32_t B, int32_t F, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                               int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs, const float* mean3,
+                               const float* std3, float* block, void* s2d, int32_t dtype_s2d, dpc_stream_t stream);
+
+/* ---- video-level test reduction (eval/test.py:317-334; csrc/lc_test.hip) ------------------------------------------------------
+ * Per-video state on the device: psum [num_class] (softmax of every window, summed), lsum [num_class] (logits summed), count [1]
+ * (windows so far) -- zero before the first video, cleared by dpc_lc_test_finish.
+ * dpc_lc_test_accumulate: logits f32 [rows][ld >= num_class]; rows [0, n_valid) are added in row order, rows beyond n_valid (the
+ *   padding of a last chunk) are never read.
+ * dpc_lc_test_finish: mean probability p and mean logit l of the video; rank = #{c : p_c > p_label} (strictly greater);
+ *   video[4] = (loss = logsumexp(l) - l[label], top-1 = rank < 1, top-5 = rank < 5, pred = argmax l with the lowest index on
+ *   ties); mean_prob [num_class] (NULL = not wanted) = p; totals f64[4] += (loss, top-1, top-5, 1); confusion i64
+ *   [num_class][num_class] gets confusion[pred][label] += 1.  No atomics: same inputs, same bits. */
+int dpc_lc_test_accumulate(const float* logits, int32_t rows, int32_t n_valid, int32_t num_class, int32_t ld, float* psum, float* lsum,
+                           int32_t* count, dpc_stream_t stream);
+int dpc_lc_test_finish(float* psum, float* lsum, int32_t* count, int32_t num_class, int32_t label, float* mean_prob, float* video,
+                       double* totals, int64_t* confusion, dpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
