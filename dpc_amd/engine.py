@@ -20,6 +20,9 @@ Data layout in HBM: activations channels-last [N][T][H][W][C] in the compute
 dtype (f32 parity mode / bf16 throughput mode); parameters stay f32 in the
 reference's state_dict layout and are repacked (K-contiguous, compute dtype) once
 per optimizer step.
+
+In file order: KernelTimer and the cost model; the conv unit and the block; ``BackboneEngine``, what the DPC-RNN step and the
+LC classifier (lc.LCEngine) share; ``DPCEngine``: the contrastive head, then the captured steps.
 """
 from __future__ import annotations
 
@@ -34,40 +37,30 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
-from .plan import LAYER_PLAN, LAYER_WIDTH, ex_supported, out_shape_of, unit_descs  # layer plan + descriptors shared with the plan query
+from .plan import LAYER_PLAN, LAYER_WIDTH, block_geometry, fold_decision, out_shape_of, unit_descs, walk_blocks  # shared with the plan query
 BN_EPS = 1e-5
 
 
 def param_shapes(network: str, widths: Sequence[int] = LAYER_WIDTH) -> "Dict[str, Tuple[int, ...]]":
     """state_dict keys/shapes of the reference DPC_RNN (without the agg.cell_list alias;
     dpc/model_3d.py:28-40, backbone/resnet_2d3d.py:205-257, backbone/convrnn.py:13-15)."""
-    if network not in LAYER_PLAN:
-        raise IOError("model type is wrong")  # backbone/select_backbone.py:19
-    plan = LAYER_PLAN[network]
     D = widths[3]
     out: Dict[str, Tuple[int, ...]] = {}
     out["backbone.conv1.weight"] = (widths[0], 3, 1, 7, 7)
     out["backbone.bn1.weight"] = (widths[0],)
     out["backbone.bn1.bias"] = (widths[0],)
-    inplanes = widths[0]
-    for li in range(4):
-        planes = widths[li]
-        k = (3, 3, 3) if li >= 2 else (1, 3, 3)
-        stride = 1 if li == 0 else 2
-        for bi in range(plan[li]):
-            pre = f"backbone.layer{li + 1}.{bi}."
-            cin = inplanes if bi == 0 else planes
-            out[pre + "conv1.weight"] = (planes, cin) + k
-            out[pre + "bn1.weight"] = (planes,)
-            out[pre + "bn1.bias"] = (planes,)
-            out[pre + "conv2.weight"] = (planes, planes) + k
-            out[pre + "bn2.weight"] = (planes,)
-            out[pre + "bn2.bias"] = (planes,)
-            if bi == 0 and (stride != 1 or inplanes != planes):
-                out[pre + "downsample.0.weight"] = (planes, inplanes, 1, 1, 1)
-                out[pre + "downsample.1.weight"] = (planes,)
-                out[pre + "downsample.1.bias"] = (planes,)
-        inplanes = planes
+    for pre, cin, planes, is3d, stride, has_ds, _ in walk_blocks(network, widths):
+        pre, k = "backbone." + pre, block_geometry(is3d, stride)[0]
+        out[pre + "conv1.weight"] = (planes, cin) + k
+        out[pre + "bn1.weight"] = (planes,)
+        out[pre + "bn1.bias"] = (planes,)
+        out[pre + "conv2.weight"] = (planes, planes) + k
+        out[pre + "bn2.weight"] = (planes,)
+        out[pre + "bn2.bias"] = (planes,)
+        if has_ds:
+            out[pre + "downsample.0.weight"] = (planes, cin, 1, 1, 1)
+            out[pre + "downsample.1.weight"] = (planes,)
+            out[pre + "downsample.1.bias"] = (planes,)
     for gate in ("reset_gate", "update_gate", "out_gate"):
         out[f"agg.ConvGRUCell_00.{gate}.weight"] = (D, 2 * D, 1, 1)
         out[f"agg.ConvGRUCell_00.{gate}.bias"] = (D,)
@@ -270,7 +263,7 @@ def _park_graphs(captures):
 class _ConvBN:
     """one Conv3d (no bias) + BatchNorm3d(batch stats) unit and its saved tensors"""
 
-    def __init__(self, eng: "DPCEngine", wname: str, bnname: str, Ci: int, Co: int, k, s, p, in_shape, stem=False):
+    def __init__(self, eng: "BackboneEngine", wname: str, bnname: str, Ci: int, Co: int, k, s, p, in_shape, stem=False):
         self.eng, self.wname, self.bnname = eng, wname, bnname
         self.Ci, self.Co, self.k, self.s, self.p, self.stem = Ci, Co, k, s, p, stem
         N, T, H, W = in_shape
@@ -340,14 +333,6 @@ class _ConvBN:
                self.mask if relu else None)
 
     # ---- backward pieces
-    def supports(self, addend: bool, gate: bool, bnred: bool) -> bool:
-        """dpc_conv_igemm_ex serves this unit's input-gradient with the given fused pieces WITHOUT demoting it from a
-        specialised kernel to the generic implicit GEMM (the plan query runs the library's own dispatch, include/dpc_hip.h)"""
-        e = self.eng
-        if self.stem or not e.fold:
-            return False
-        return ex_supported(e.lib, self.desc_d, addend, gate, bnred)
-
     def bn_backward(self, dy: torch.Tensor, y: Optional[torch.Tensor], relu: bool, dx: torch.Tensor,
                     dz: Optional[torch.Tensor] = None, ext_mask: Optional[torch.Tensor] = None):
         """BatchNorm backward of this unit: dz = dy gated by the ReLU that follows it (its own sign mask, or `ext_mask`: the
@@ -423,15 +408,13 @@ class _Block:
 
     def __init__(self, eng, pre: str, Ci: int, Co: int, is3d: bool, stride: int, in_shape, has_ds: bool, final_relu: bool):
         self.eng = eng
-        k = (3, 3, 3) if is3d else (1, 3, 3)
-        p = (1, 1, 1) if is3d else (0, 1, 1)
-        s = (stride,) * 3 if is3d else (1, stride, stride)
+        k, s, p = block_geometry(is3d, stride)
         self.c1 = _ConvBN(eng, pre + "conv1.weight", pre + "bn1", Ci, Co, k, s, p, in_shape)
         self.c2 = _ConvBN(eng, pre + "conv2.weight", pre + "bn2", Co, Co, k, (1, 1, 1), p, self.c1.out_shape)
         self.ds = _ConvBN(eng, pre + "downsample.0.weight", pre + "downsample.1", Ci, Co, (1, 1, 1), s, (0, 0, 0),
                           in_shape) if has_ds else None
         self.final_relu = final_relu
-        self.site = pre[len("backbone."):]   # "layer2.0.": names this block's side-stream sites (DPCEngine.side_off)
+        self.site = pre[len("backbone."):]   # "layer2.0.": names this block's side-stream sites (BackboneEngine.side_off)
         self.out_shape = self.c2.out_shape
         self.Co = Co
         self.act1 = eng.empty(self.c1.out_shape + (Co,), eng.cdtype)
@@ -454,14 +437,12 @@ class _Block:
         return self.out
 
     def plan_backward(self, prev: "Optional[_Block]"):
-        """which backward pieces ride in input-gradient epilogues (decided once; dpc_conv_igemm_ex + the plan query):
-        fold_c1   conv2's input-gradient takes bn1's backward reduction;
-        gate      conv1's input-gradient adds the block's incoming gradient gated by the output ReLU mask (no dz tensor);
-        fold_prev ... and takes the backward reduction of the PREVIOUS block's bn2, whose output gradient it writes."""
+        """which backward pieces ride in input-gradient epilogues (decided once): plan.fold_decision, under the engine's switches"""
+        e = self.eng
+        fold_c1, gate, fold_prev = (False, False, False) if not e.fold else fold_decision(
+            e.lib, self.c1.desc_d, self.c2.desc_d, self.ds is not None, self.final_relu, prev is not None)
         red = bool(int(os.environ.get("DPC_FOLD_RED", "1")))   # probe: the reductions as their own launches, the gated addend stays fused
-        self.fold_c1 = red and self.c2.supports(False, False, True)
-        self.gate = self.ds is None and self.c1.supports(True, self.final_relu, False)
-        self.fold_prev = bool(red and prev is not None and self.gate and self.c1.supports(True, self.final_relu, True))
+        self.fold_c1, self.gate, self.fold_prev = red and fold_c1, gate, red and fold_prev
         self.prev = prev
 
     def backward(self, dout: torch.Tensor, need_dx: bool = True) -> Optional[torch.Tensor]:
@@ -516,10 +497,10 @@ class _Block:
 
 
 # live engines by the address of their parameter arena (weak: an engine dies with its owner)
-ENGINES: "weakref.WeakValueDictionary[int, DPCEngine]" = weakref.WeakValueDictionary()
+ENGINES: "weakref.WeakValueDictionary[int, BackboneEngine]" = weakref.WeakValueDictionary()
 
 
-def engine_of(param: torch.Tensor) -> "Optional[DPCEngine]":
+def engine_of(param: torch.Tensor) -> "Optional[BackboneEngine]":
     """the engine whose flat parameter arena `param` is a view of (None: an ordinary tensor)"""
     a = param.data_ptr()
     for base, eng in list(ENGINES.items()):
@@ -528,22 +509,23 @@ def engine_of(param: torch.Tensor) -> "Optional[DPCEngine]":
     return None
 
 
-class DPCEngine:
-    BN_RUNNING = False
+class BackboneEngine:
+    """What both models run on: the flat arenas and their offsets, streams and scratch, the 2d3d-ResNet with its backward, the
+    ConvGRU host wiring, the device counters and the fused Adam.  A head (DPCEngine below, lc.LCEngine) calls this constructor
+    with its parameter shapes, builds its own buffers (_build_gru for the recurrence) and ends with _finish_buffers()."""
     BN_MOMENTUM = 0.1  # torch.nn.BatchNorm3d default
 
-    def __init__(self, network: str = "resnet18", sample_size: int = 128, num_seq: int = 8, seq_len: int = 5,
-                 pred_step: int = 3, batch: int = 4, device="cuda", compute_dtype=torch.float32,
-                 widths: Sequence[int] = LAYER_WIDTH, lib: Optional[L.Lib] = None,
-                 lr: float = 1e-3, wd: float = 1e-5, dropout: float = 0.1, seed: int = 233, score_path: str = "auto", stem_fused: bool | None = None,
-                 fold: bool | None = None, reserve_cus: int | None = None, f32_matmul: str | None = None):
+    def __init__(self, shapes: "Dict[str, Tuple[int, ...]]", network: str, sample_size: int, num_seq: int, seq_len: int, batch: int,
+                 device, compute_dtype, widths: Sequence[int], lib: Optional[L.Lib], lr: float, wd: float, gru_dropout: float, seed: int,
+                 stem_fused: bool | None = None, fold: bool | None = None, reserve_cus: int | None = None,
+                 f32_matmul: str | None = None, bn_running: bool = False):
         self.device = torch.device(device)
         self.lib = L.lib_for(self.device, lib)  # raises unless HIP device (or an explicit simulator handle in tests)
         self.cdtype = compute_dtype
-        self.network, self.size, self.N, self.SL, self.P, self.B = network, sample_size, num_seq, seq_len, pred_step, batch
+        self.network, self.size, self.N, self.SL, self.B = network, sample_size, num_seq, seq_len, batch
         self.widths = tuple(widths)
         self.D = widths[3]
-        self.lr, self.wd, self.p_drop = lr, wd, dropout
+        self.lr, self.wd, self.p_drop = lr, wd, gru_dropout
         self.last_duration = int(math.ceil(seq_len / 4))   # dpc/model_3d.py:24
         self.last_size = int(math.ceil(sample_size / 32))  # dpc/model_3d.py:25
         self.SQ = self.last_size ** 2
@@ -554,16 +536,12 @@ class DPCEngine:
         self._scratch: Dict[Tuple[int, ...], List[torch.Tensor]] = {}
         self._step_count = 0
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
-        self.score_mode = "materialised"  # what the last train step ran ("fused": no [R][R] tensor in HBM)
         self.timer: Optional["KernelTimer"] = None
         self._tag: Optional[str] = None
-        self._capture_events: Optional[list] = None   # fork / join events of the capture in progress (capture_train_step)
-        self._captures: Dict[tuple, object] = {}   # capture_train_step results by (input buffer, exchange, carve-out)
-        self._capture_graphs: list = []            # their _Capture records; parked in _LIVE_GRAPHS when the engine goes (see there)
-        weakref.finalize(self, _park_graphs, self._capture_graphs)
+        self._capture_events: Optional[list] = None   # fork / join events of the capture in progress (DPCEngine._capture)
+        self._carved = False   # a CU carve-out for RCCL is in force (_backbone_backward sets it, _uncarve lifts it)
 
         # ---- flat f32 arenas: parameters, gradients, Adam moments
-        self._score_path = score_path
         # Fused stem weight gradient (csrc/conv_wgrad_stem.hip: no full-resolution dz tensor, bit-identical to the two-kernel form).
         # Round 2's register-gather version was slower than the two kernels and opt-in; the LDS-DMA rebuild of round 3 is faster in
         # the step (4 667 against 4 617 clips/s at cfg2) and the default; DPC_STEM_FUSED=0 / stem_fused=False run the two kernels.
@@ -585,7 +563,6 @@ class DPCEngine:
         self.f32_matmul = mm
         self._x6 = 1 if (mm == "bf16x6" and compute_dtype == torch.float32) else 0
         self._pack_table = None
-        self._gate_table = None
         # weight gradients on a second stream beside the next unit's BatchNorm backward (side() below); DPC_WGRAD_STREAM=0: one stream.
         # What goes there: conv2 / downsample weight gradients, conv1's, the head's parameter gradients, the per-step weight repacks;
         # the main stream waits for the side stream before every input-gradient (side()).  Rounds 3-4 had switches for both choices
@@ -594,10 +571,10 @@ class DPCEngine:
         self._on_side = False
         self.side_off = frozenset(x for x in os.environ.get("DPC_SIDE_OFF", "").split(",") if x)   # probe knob (scripts/probes/side_sites.py)
         self._busy = []   # [(event recorded on the side stream, scratch buffers its launches read)], oldest first
-        self.bn_running = type(self).BN_RUNNING  # BatchNorm3d with running statistics (the LC classifier's backbone)
+        self.bn_running = bool(bn_running)  # BatchNorm3d with running statistics (the LC classifier's backbone)
         self.train_mode = True       # only matters when bn_running: eval uses the running buffers
         self.BUF: Dict[str, torch.Tensor] = {}
-        self.shapes = self._param_shapes()
+        self.shapes = shapes
         self.offsets: Dict[str, Tuple[int, int]] = {}
         off = 0
         for k, shp in self.shapes.items():
@@ -626,22 +603,15 @@ class DPCEngine:
         self.pooled = self.empty(self.pool_shape + (widths[0],), dt)
         self.pool_arg = torch.empty(self.pool_shape + (widths[0],), dtype=torch.uint8, device=self.device)
         self.blocks: List[_Block] = []
-        shape, inplanes = self.pool_shape, widths[0]
-        plan = LAYER_PLAN[network]
-        for li in range(4):
-            planes = widths[li]
-            for bi in range(plan[li]):
-                stride = 2 if (li > 0 and bi == 0) else 1
-                has_ds = bi == 0 and (stride != 1 or inplanes != planes)
-                last = li == 3 and bi == plan[li] - 1
-                blk = _Block(self, f"backbone.layer{li + 1}.{bi}.", inplanes if bi == 0 else planes, planes, li >= 2, stride,
-                             shape, has_ds, final_relu=not last)
-                self.blocks.append(blk)
-                shape, inplanes = blk.out_shape, planes
+        shape = self.pool_shape
+        for pre, cin, planes, is3d, stride, has_ds, last in walk_blocks(network, widths):
+            blk = _Block(self, "backbone." + pre, cin, planes, is3d, stride, shape, has_ds, final_relu=not last)
+            self.blocks.append(blk)
+            shape = blk.out_shape
         for i, blk in enumerate(self.blocks):
             blk.plan_backward(self.blocks[i - 1] if i > 0 else None)
         # gradient-arena split for the overlapped all-reduce: the head = stem + layer1 (finished last by the backward)
-        self.n_head_blocks = plan[0]
+        self.n_head_blocks = LAYER_PLAN[network][0]
         self.grad_split = self.offsets["backbone.layer2.0.conv1.weight"][0]
         self.feat_shape = shape
         if shape[1] != self.last_duration or shape[2] != self.last_size or shape[3] != self.last_size:
@@ -649,27 +619,27 @@ class DPCEngine:
                              f"({self.last_duration},{self.last_size}); see dpc/model_3d.py:24-25,53-55")
         self.units: List[_ConvBN] = [self.stem] + [u for b in self.blocks for u in b.units()]
 
-        self._build_head()
-        self._finish_buffers()
+        # optimizer-step counter and Adam bias corrections in device memory: a captured hipGraph advances them on replay
+        self.dev_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.dev_bc = torch.ones(2, dtype=torch.float32, device=self.device)
+        # dropout draw counter: every train-mode forward advances it, the recurrence keys its Philox masks on it.  Not the optimizer
+        # step: the nn.Module boundary with an external torch optimizer never runs adam_step() and would redraw one mask forever
+        self.dev_draw = torch.zeros(1, dtype=torch.int32, device=self.device)
 
-    # ---- head of DPC_RNN: ConvGRU aggregate/predict, contrastive score, loss (subclasses build another head)
-    def _param_shapes(self):
-        return param_shapes(self.network, self.widths)
-
-    def _build_head(self):
-        batch, pred_step, num_seq, widths, dt = self.B, self.P, self.N, self.widths, self.cdtype
-        score_path = self._score_path
-        # ---- ConvGRU / predictor / score buffers.  rows M = (b, s)
-        B, P, SQ, D, N = batch, pred_step, self.SQ, self.D, num_seq
-        M = B * SQ
-        self.M = M
-        self.n_agg = N - P                     # aggregation steps (dpc/model_3d.py:62)
-        self.n_steps = self.n_agg + P - 1      # the GRU step after the last prediction is dead code (model_3d.py:70-72)
-        f32 = torch.float32
+    # ---- ConvGRU host wiring (backbone/convrnn.py:24-34,62-88), one copy for both heads: buffers, sizing, the descriptor's common
+    # fields here; the pack in pack_weights; the parameter gradients in _gru_param_grads
+    def _build_gru(self, n_agg: int, n_steps: int, P: int):
+        """the recurrence over n_steps steps, the first n_agg of them aggregation (rows M = (b, s)); the head adds its own
+        descriptor fields to self.gru_desc"""
+        N, D, SQ, dt, f32 = self.N, self.D, self.SQ, self.cdtype, torch.float32
+        # the recurrence runs as two launches (dpc_gru_chain_fwd / _bwd, csrc/gru_chain.hip): fragment-major packed weights,
+        # f32 scratch of the backward kernel, and the descriptor with every (static) buffer address
+        if D % 32 or D > 256:
+            raise ValueError("feature size must be a multiple of 32, at most 256 (fused ConvGRU recurrence)")
+        M = self.B * SQ
+        ns = n_steps
+        self.M, self.n_agg, self.n_steps = M, n_agg, ns
         self.feat_relu = self.empty((N, M, D), dt)    # [n][(b,s)][d]; slots [0,n_steps) double as the GRU inputs
-        self.feat_inf = self.empty((B, P, SQ, D), dt)
-        self.pred = self.empty((B, P, SQ, D), dt)
-        ns = self.n_steps
         self.X_all = self.feat_relu[:ns]              # GRU inputs x_t (agg: feat_relu[t]; predict: relu(p_t) overwrites
                                                       # the slots of the last P blocks, whose ReLU'd features are unused)
         self.H_all = torch.zeros((ns + 1, M, D), dtype=dt, device=self.device)   # h_0 = 0 (never written), h_t after dropout
@@ -677,64 +647,10 @@ class DPCEngine:
         self.G_all = self.empty((ns, M, 3 * D), dt)   # [dpu | dpr | dpo] per step
         self.U_all, self.R_all, self.O_all = (self.empty((ns, M, D), f32) for _ in range(3))
         self.drop_all: Optional[torch.Tensor] = None
-        # optimizer-step counter and Adam bias corrections in device memory: a captured hipGraph advances them on replay
-        self.dev_step = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.dev_bc = torch.ones(2, dtype=f32, device=self.device)
-        # dropout draw counter: every train-mode forward advances it, the recurrence keys its Philox masks on it.  Not the optimizer
-        # step: the nn.Module boundary with an external torch optimizer never runs adam_step() and would redraw one mask forever
-        self.dev_draw = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.P1_all = self.empty((P, M, D), dt)       # relu(W1 h + b1)
-        self.dP1 = self.empty((P, M, D), dt)          # grads at the pre-activations of network_pred
-        self.dP2 = self.empty((P, M, D), dt)
-        self.Hpred = self.H_all[self.n_agg:]          # hidden state each prediction was made from
-        R = B * P * SQ
-        self.R = R
-        self.score = self.empty((R, R), f32)
-        E = 8 if dt == torch.bfloat16 else 4
-        self.ld_d = (R + E - 1) // E * E
-        self.dscore = self.empty((R, self.ld_d), dt)
-        self.row_ws = self.empty((R, 2), f32)
-        self.result = self.empty((4,), f32)
-        self.predT = torch.zeros((D, self.ld_d), dtype=dt, device=self.device)   # transposed operands of the score backward
-        self.finfT = torch.zeros((D, self.ld_d), dtype=dt, device=self.device)   # (columns >= R stay zero)
-        # The score + loss of a bf16 train step, two ways (csrc/score_fused.hip):
-        #   "materialised": score GEMM -> [R][R] f32 in HBM -> CE / top-k / dS (bf16) -> two split-K GEMMs;
-        #   "fused": LSE, target logit and rank inside the forward contraction, dS recomputed inside the two backward contractions -- no
-        #            [R][R] tensor in HBM (151 MB + 75 MB at cfg2, 983 MB + 492 MB at cfg5).
-        # Measured on MI355X: at R = 6 144 the materialised step wins clearly (fused backward 2 x 140 us against 2 x 37 us: exp() is
-        # quarter rate and K = 256 gives the matrix cores too little to hide it behind); at R = 15 680 it wins by 1.5 % of the step
-        # (813 against 801 clips/s at cfg5, round 4).  288 GB of HBM make the 1.5 GB a non-issue, so "auto" = materialised at every
-        # size since round 5 (round 2-4: fused from R = 8 192); "fused" keeps the other path selectable (bench.py --score-path fused).
-        if score_path not in ("auto", "fused", "materialised"):
-            raise ValueError("score_path must be auto, fused or materialised")
-        fusable = dt == torch.bfloat16 and D in (256, 32)
-        self.score_fusable = fusable and score_path == "fused"
-        self._score_fused = False
-        if self.score_fusable:
-            nf, nb = C.c_int64(0), C.c_int64(0)
-            self.lib.call("dpc_score_ws_floats", R, D, C.byref(nf), C.byref(nb))
-            self.score_ws = self.empty((max(nf.value, nb.value),), f32)
-            self.score_diag, self.score_lse2 = self.empty((R,), f32), self.empty((R,), f32)
-        # bf16 LOGITS for the step that does not return its score (train_step / capture_train_step / validate: forward(materialise=False)):
-        # the score GEMM writes, and the loss kernel reads, [R][R] in the compute dtype -- 75 MB instead of 151 MB each way at cfg2,
-        # 492 instead of 983 MB at cfg5.  forward(materialise=True) -- the module boundary, everything that looks at the score -- keeps
-        # f32.  Needs whole 128-byte rows (R a multiple of 64: cfg2 6 144, cfg5 15 680; cfg4's 6 468 keeps f32); DPC_SCORE_BF16=0: off.
-        self.score16 = None
-        if dt == torch.bfloat16 and R % 64 == 0 and R <= 16384 and D in (256, 32) and not self.score_fusable and int(os.environ.get("DPC_SCORE_BF16", "1")):
-            self.score16 = self.empty((R, R), dt)
-        self._score16_live = False
-        self.d_pred = self.empty((B, P, SQ, D), f32)
-        self.d_finf = self.empty((B, P, SQ, D), f32)
-        self.d_featrelu = self.empty((self.n_agg, M, D), f32)
-        self.d_feat = self.empty(self.feat_shape + (widths[3],), dt)
-        self.mask: Optional[torch.Tensor] = None
-        # the recurrence runs as two launches (dpc_gru_chain_fwd / _bwd, csrc/gru_chain.hip): fragment-major packed weights,
-        # f32 scratch of the backward kernel, and the descriptor with every (static) buffer address
-        if D % 32 or D > 256:
-            raise ValueError("feature size must be a multiple of 32, at most 256 (fused ConvGRU recurrence)")
+        self.d_featrelu = self.empty((n_agg, M, D), f32)
+        self.d_feat = self.empty(self.feat_shape + (D,), dt)
         self.gru_packed = self.empty((16 * D * D,), dt)
         self.gru_ws = self.empty((2, M, D), f32)
-        self.gru_desc = L.GruChainDesc()
         self.dWx = self.empty((3 * D, D), f32)
         self.dWh = self.empty((2 * D, D), f32)
         self.dWo = self.empty((D, D), f32)
@@ -742,27 +658,48 @@ class DPCEngine:
         for (co, kk) in ((3 * D, D), (2 * D, D), (D, D)):
             self._need_wgrad(ns * M, co, kk)
         self.need_part(64 * 3 * D)  # dpc_colsum workspace
-        self._need_wgrad(R, R, D)
-        nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
-        self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
-        self.need_part(nsk.value * R * D)
-        # d_feature_inf = dS^T @ pred on the loader / compute kernel with dS read K-major (csrc/gemm_ws.hip); None: weight-gradient kernel
-        self._tn_splits = None
-        if dt == torch.bfloat16:
-            rc = self.lib._fn("dpc_gemm_tn_splitk")(L.dtype_code(dt), R, D, R, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
-            if rc == 0:
-                self._tn_splits = nsk.value
-                self.need_part(nsk.value * R * D)
-        gd, Pm = self.gru_desc, self.PRM
-        gd.dtype, gd.M, gd.D, gd.SQ, gd.P, gd.n_agg, gd.n_steps = L.dtype_code(dt), M, D, SQ, P, self.n_agg, ns
+        self._gate_table = None
+        gd, Pm = L.GruChainDesc(), self.PRM
+        gd.dtype, gd.M, gd.D, gd.SQ, gd.P, gd.n_agg, gd.n_steps = L.dtype_code(dt), M, D, SQ, P, n_agg, ns
         gd.p_drop, gd.seed = float(self.p_drop), self.seed
         for name, t in (("packed", self.gru_packed), ("bias_u", Pm["agg.ConvGRUCell_00.update_gate.bias"]),
                         ("bias_r", Pm["agg.ConvGRUCell_00.reset_gate.bias"]), ("bias_o", Pm["agg.ConvGRUCell_00.out_gate.bias"]),
-                        ("bias_1", Pm["network_pred.0.bias"]), ("bias_2", Pm["network_pred.2.bias"]), ("X_all", self.X_all),
-                        ("H_all", self.H_all), ("HR_all", self.HR_all), ("U_all", self.U_all), ("R_all", self.R_all),
-                        ("O_all", self.O_all), ("P1_all", self.P1_all), ("pred", self.pred), ("d_pred", self.d_pred),
-                        ("G_all", self.G_all), ("dP1", self.dP1), ("dP2", self.dP2), ("d_x", self.d_featrelu), ("ws", self.gru_ws)):
+                        ("X_all", self.X_all), ("H_all", self.H_all), ("HR_all", self.HR_all), ("U_all", self.U_all),
+                        ("R_all", self.R_all), ("O_all", self.O_all), ("G_all", self.G_all), ("d_x", self.d_featrelu),
+                        ("ws", self.gru_ws)):
             setattr(gd, name, t.data_ptr())
+        self.gru_desc = gd
+
+    def _gru_param_grads(self, dc):
+        """weight / bias gradients of the ConvGRU, batched over all steps, into the gradient arena (on whichever stream the head
+        issues them)"""
+        D, M, ns, Gm = self.D, self.M, self.n_steps, self.G
+        self.gemm_tn(self.G_all, 3 * D, self.X_all, D, self.dWx, ns * M, 3 * D, D)
+        self.gemm_tn(self.G_all, 3 * D, self.H_all, D, self.dWh, ns * M, 2 * D, D)
+        self.gemm_tn(self.G_all[:, :, 2 * D:], 3 * D, self.HR_all, D, self.dWo, ns * M, D, D)
+        self.call("dpc_colsum", self.G_all, dc, 3 * D, ns * M, 3 * D, self.db, 0, self.part, self.part.numel())
+        if self._gate_table is None:   # the nine gate slices in one launch (static table: addresses never change)
+            ents = []
+            for i, (g, n) in enumerate((("u", "update_gate"), ("r", "reset_gate"), ("o", "out_gate"))):
+                w = Gm[f"agg.ConvGRUCell_00.{n}.weight"].view(D, 2 * D)   # [D][x half | h half]
+                ents += [(self.dWx[i * D:(i + 1) * D], D, w, 2 * D, D, D),
+                         (self.dWh[i * D:(i + 1) * D] if g != "o" else self.dWo, D, w[:, D:], 2 * D, D, D),
+                         (self.db[i * D:(i + 1) * D], D, Gm[f"agg.ConvGRUCell_00.{n}.bias"], D, 1, D)]
+            tab = (L.Copy2dEntry * len(ents))()
+            blk = 0
+            for i, (src, sld, dst, dld, r, c) in enumerate(ents):
+                tab[i] = L.Copy2dEntry(src.data_ptr(), dst.data_ptr(), sld, dld, r, c, blk, 0)
+                blk += max(1, min(64, (r * c + 1023) // 1024))
+            raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone()
+            self._gate_table = (raw.to(self.device), len(ents), blk)
+        self.call("dpc_copy2d_multi", *self._gate_table)
+
+    def dropout_masks_of_step(self) -> torch.Tensor:
+        """[n_steps, M, D] pre-scaled keep masks the recurrence kernels generated in the LAST train-mode forward (same Philox
+        stream at the current draw counter, materialised by dpc_dropout_mask): diagnostics and tests."""
+        buf = self.empty((self.n_steps, self.M, self.D), torch.float32)
+        self.call("dpc_dropout_mask", buf, buf.numel(), float(self.p_drop), self.seed, self.dev_draw)
+        return buf
 
     def _finish_buffers(self):
         widths, dt, f32 = self.widths, self.cdtype, torch.float32
@@ -942,7 +879,7 @@ class DPCEngine:
             dst.copy_(v.to(torch.float32).reshape(shp))
         self.packed_for_step = -1
 
-    def adopt_optimizer_state(self, old: "DPCEngine"):
+    def adopt_optimizer_state(self, old: "BackboneEngine"):
         """continue `old`'s optimisation in this engine (same network, any batch / compute dtype / device): Adam moments, the
         optimizer-step counter with its device-side bias corrections, the dropout draw counter, lr / weight decay.  The module
         boundary rebuilds its engine when the batch size, model.bfloat16() / .float() or the device change (model._ensure_engine);
@@ -1072,9 +1009,125 @@ class DPCEngine:
         self._uncarve()
 
     def _uncarve(self):
-        if getattr(self, "_carved", False):
+        if self._carved:
             self.lib.call("dpc_set_reserved_cus", 0)
             self._carved = False
+
+    @property
+    def step_count(self) -> int:
+        """completed optimizer steps (host mirror of dev_step)"""
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, t: int):  # checkpoint resume: host value -> device counter
+        self._step_count = int(t)
+        self.dev_step.fill_(int(t))
+        self.dev_draw.fill_(int(t))  # one draw per step in the engine-owned loop: a resumed run continues the same mask stream
+
+    def adam_step(self, grad_scale: float = 1.0):
+        self._step_count += 1
+        self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
+        self.call("dpc_adam_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
+                  self.wd, self.dev_bc, grad_scale)
+
+    def _backward_and_exchange(self, allreduce=None):
+        """the head's backward(), then the gradient exchange: two buckets (``allreduce.start`` on the tail while layer1 + stem
+        are still running, ``allreduce.finish`` on the rest) or one call on the whole arena"""
+        if allreduce is not None and hasattr(allreduce, "start"):
+            self.backward(on_tail_ready=allreduce.start)
+            allreduce.finish(self.flat_g[:self.grad_split])
+        else:
+            self.backward()
+            if allreduce is not None:
+                allreduce(self.flat_g)
+
+
+class DPCEngine(BackboneEngine):
+    """the DPC-RNN step: backbone + ConvGRU aggregate / predict, contrastive score, loss, and the captured steps"""
+
+    def __init__(self, network: str = "resnet18", sample_size: int = 128, num_seq: int = 8, seq_len: int = 5,
+                 pred_step: int = 3, batch: int = 4, device="cuda", compute_dtype=torch.float32,
+                 widths: Sequence[int] = LAYER_WIDTH, lib: Optional[L.Lib] = None,
+                 lr: float = 1e-3, wd: float = 1e-5, dropout: float = 0.1, seed: int = 233, score_path: str = "auto", stem_fused: bool | None = None,
+                 fold: bool | None = None, reserve_cus: int | None = None, f32_matmul: str | None = None):
+        self.P = pred_step
+        self.score_mode = "materialised"  # what the last train step ran ("fused": no [R][R] tensor in HBM)
+        self._captures: Dict[tuple, object] = {}   # capture_train_step results by (input buffer, exchange, carve-out)
+        self._capture_graphs: list = []            # their _Capture records; parked in _LIVE_GRAPHS when the engine goes (see there)
+        weakref.finalize(self, _park_graphs, self._capture_graphs)
+        super().__init__(param_shapes(network, widths), network, sample_size, num_seq, seq_len, batch, device, compute_dtype, widths, lib,
+                         lr, wd, dropout, seed, stem_fused, fold, reserve_cus, f32_matmul)
+        self._build_head(score_path)
+        self._finish_buffers()
+
+    # ---- head of DPC_RNN: ConvGRU aggregate/predict, contrastive score, loss
+    def _build_head(self, score_path: str):
+        dt, f32 = self.cdtype, torch.float32
+        B, P, SQ, D, N = self.B, self.P, self.SQ, self.D, self.N
+        if score_path not in ("auto", "fused", "materialised"):
+            raise ValueError("score_path must be auto, fused or materialised")
+        # ---- ConvGRU / predictor / score buffers.  rows M = (b, s); N - P aggregation steps (dpc/model_3d.py:62), and the GRU step
+        # after the last prediction is dead code (model_3d.py:70-72)
+        self._build_gru(n_agg=N - P, n_steps=(N - P) + P - 1, P=P)
+        M = self.M
+        self.feat_inf = self.empty((B, P, SQ, D), dt)
+        self.pred = self.empty((B, P, SQ, D), dt)
+        self.P1_all = self.empty((P, M, D), dt)       # relu(W1 h + b1)
+        self.dP1 = self.empty((P, M, D), dt)          # grads at the pre-activations of network_pred
+        self.dP2 = self.empty((P, M, D), dt)
+        self.Hpred = self.H_all[self.n_agg:]          # hidden state each prediction was made from
+        R = B * P * SQ
+        self.R = R
+        self.score = self.empty((R, R), f32)
+        E = 8 if dt == torch.bfloat16 else 4
+        self.ld_d = (R + E - 1) // E * E
+        self.dscore = self.empty((R, self.ld_d), dt)
+        self.row_ws = self.empty((R, 2), f32)
+        self.result = self.empty((4,), f32)
+        self.predT = torch.zeros((D, self.ld_d), dtype=dt, device=self.device)   # transposed operands of the score backward
+        self.finfT = torch.zeros((D, self.ld_d), dtype=dt, device=self.device)   # (columns >= R stay zero)
+        # The score + loss of a bf16 train step, two ways (csrc/score_fused.hip):
+        #   "materialised": score GEMM -> [R][R] f32 in HBM -> CE / top-k / dS (bf16) -> two split-K GEMMs;
+        #   "fused": LSE, target logit and rank inside the forward contraction, dS recomputed inside the two backward contractions -- no
+        #            [R][R] tensor in HBM (151 MB + 75 MB at cfg2, 983 MB + 492 MB at cfg5).
+        # Measured on MI355X: at R = 6 144 the materialised step wins clearly (fused backward 2 x 140 us against 2 x 37 us: exp() is
+        # quarter rate and K = 256 gives the matrix cores too little to hide it behind); at R = 15 680 it wins by 1.5 % of the step
+        # (813 against 801 clips/s at cfg5, round 4).  288 GB of HBM make the 1.5 GB a non-issue, so "auto" = materialised at every
+        # size since round 5 (round 2-4: fused from R = 8 192); "fused" keeps the other path selectable (bench.py --score-path fused).
+        fusable = dt == torch.bfloat16 and D in (256, 32)
+        self.score_fusable = fusable and score_path == "fused"
+        self._score_fused = False
+        if self.score_fusable:
+            nf, nb = C.c_int64(0), C.c_int64(0)
+            self.lib.call("dpc_score_ws_floats", R, D, C.byref(nf), C.byref(nb))
+            self.score_ws = self.empty((max(nf.value, nb.value),), f32)
+            self.score_diag, self.score_lse2 = self.empty((R,), f32), self.empty((R,), f32)
+        # bf16 LOGITS for the step that does not return its score (train_step / capture_train_step / validate: forward(materialise=False)):
+        # the score GEMM writes, and the loss kernel reads, [R][R] in the compute dtype -- 75 MB instead of 151 MB each way at cfg2,
+        # 492 instead of 983 MB at cfg5.  forward(materialise=True) -- the module boundary, everything that looks at the score -- keeps
+        # f32.  Needs whole 128-byte rows (R a multiple of 64: cfg2 6 144, cfg5 15 680; cfg4's 6 468 keeps f32); DPC_SCORE_BF16=0: off.
+        self.score16 = None
+        if dt == torch.bfloat16 and R % 64 == 0 and R <= 16384 and D in (256, 32) and not self.score_fusable and int(os.environ.get("DPC_SCORE_BF16", "1")):
+            self.score16 = self.empty((R, R), dt)
+        self._score16_live = False
+        self.d_pred = self.empty((B, P, SQ, D), f32)
+        self.d_finf = self.empty((B, P, SQ, D), f32)
+        self.mask: Optional[torch.Tensor] = None
+        self._need_wgrad(R, R, D)
+        nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
+        self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
+        self.need_part(nsk.value * R * D)
+        # d_feature_inf = dS^T @ pred on the loader / compute kernel with dS read K-major (csrc/gemm_ws.hip); None: weight-gradient kernel
+        self._tn_splits = None
+        if dt == torch.bfloat16:
+            rc = self.lib._fn("dpc_gemm_tn_splitk")(L.dtype_code(dt), R, D, R, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
+            if rc == 0:
+                self._tn_splits = nsk.value
+                self.need_part(nsk.value * R * D)
+        gd, Pm = self.gru_desc, self.PRM
+        for name, t in (("bias_1", Pm["network_pred.0.bias"]), ("bias_2", Pm["network_pred.2.bias"]), ("P1_all", self.P1_all),
+                        ("pred", self.pred), ("d_pred", self.d_pred), ("dP1", self.dP1), ("dP2", self.dP2)):
+            setattr(gd, name, t.data_ptr())
 
     def forward(self, block: torch.Tensor, train: bool = False, dropout_masks: Optional[torch.Tensor] = None,
                 materialise: bool = True, new_draw: bool = True):
@@ -1127,13 +1180,6 @@ class DPCEngine:
         with self.tag("score"):
             self.gemm(self.pred, self.feat_inf, self.score, R, R, D)
         return self.score.view(B, P, SQ, B, P, SQ)
-
-    def dropout_masks_of_step(self) -> torch.Tensor:
-        """[n_steps, M, D] pre-scaled keep masks the recurrence kernels generated in the LAST train-mode forward (same Philox
-        stream at the current draw counter, materialised by dpc_dropout_mask): diagnostics and tests."""
-        buf = self.empty((self.n_steps, self.M, self.D), torch.float32)
-        self.call("dpc_dropout_mask", buf, buf.numel(), float(self.p_drop), self.seed, self.dev_draw)
-        return buf
 
     def get_mask(self) -> torch.Tensor:
         if self.mask is None:
@@ -1199,7 +1245,6 @@ class DPCEngine:
                 else:
                     self.gemm_tn(self.dscore, self.ld_d, self.pred, D, self.d_finf, R, R, D)
         # ---- predict loop + aggregation, reversed: one launch (G_all, dP1, dP2, d_featrelu come back)
-        ns = self.n_steps
         self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
         # ---- temporal pool / split: the backbone's incoming gradient (the main stream's critical path goes on into the backbone)
         fs = self.feat_shape
@@ -1212,77 +1257,29 @@ class DPCEngine:
         return self.d_feat
 
     def _head_param_grads(self, dc):
-        D, M, P, ns = self.D, self.M, self.P, self.n_steps
-        Gm = self.G
-        self.gemm_tn(self.G_all, 3 * D, self.X_all, D, self.dWx, ns * M, 3 * D, D)
-        self.gemm_tn(self.G_all, 3 * D, self.H_all, D, self.dWh, ns * M, 2 * D, D)
-        self.gemm_tn(self.G_all[:, :, 2 * D:], 3 * D, self.HR_all, D, self.dWo, ns * M, D, D)
-        self.call("dpc_colsum", self.G_all, dc, 3 * D, ns * M, 3 * D, self.db, 0, self.part, self.part.numel())
-        if self._gate_table is None:   # the nine gate slices in one launch (static table: addresses never change)
-            ents = []
-            for i, (g, n) in enumerate((("u", "update_gate"), ("r", "reset_gate"), ("o", "out_gate"))):
-                w = Gm[f"agg.ConvGRUCell_00.{n}.weight"].view(D, 2 * D)   # [D][x half | h half]
-                ents += [(self.dWx[i * D:(i + 1) * D], D, w, 2 * D, D, D),
-                         (self.dWh[i * D:(i + 1) * D] if g != "o" else self.dWo, D, w[:, D:], 2 * D, D, D),
-                         (self.db[i * D:(i + 1) * D], D, Gm[f"agg.ConvGRUCell_00.{n}.bias"], D, 1, D)]
-            tab = (L.Copy2dEntry * len(ents))()
-            blk = 0
-            for i, (src, sld, dst, dld, r, c) in enumerate(ents):
-                tab[i] = L.Copy2dEntry(src.data_ptr(), dst.data_ptr(), sld, dld, r, c, blk, 0)
-                blk += max(1, min(64, (r * c + 1023) // 1024))
-            raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).clone()
-            self._gate_table = (raw.to(self.device), len(ents), blk)
-        self.call("dpc_copy2d_multi", *self._gate_table)
+        D, M, P, Gm = self.D, self.M, self.P, self.G
+        self._gru_param_grads(dc)
         self.gemm_tn(self.dP1, D, self.Hpred, D, Gm["network_pred.0.weight"].view(D, D), P * M, D, D)
         self.gemm_tn(self.dP2, D, self.P1_all, D, Gm["network_pred.2.weight"].view(D, D), P * M, D, D)
         self.call("dpc_colsum", self.dP1, dc, D, P * M, D, Gm["network_pred.0.bias"], 0, self.part, self.part.numel())
         self.call("dpc_colsum", self.dP2, dc, D, P * M, D, Gm["network_pred.2.bias"], 0, self.part, self.part.numel())
 
-    @property
-    def step_count(self) -> int:
-        """completed optimizer steps (host mirror of dev_step)"""
-        return self._step_count
-
-    @step_count.setter
-    def step_count(self, t: int):  # checkpoint resume: host value -> device counter
-        self._step_count = int(t)
-        self.dev_step.fill_(int(t))
-        self.dev_draw.fill_(int(t))  # one draw per step in the engine-owned loop: a resumed run continues the same mask stream
-
-    def adam_step(self, grad_scale: float = 1.0):
-        self._step_count += 1
-        self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
-        self.call("dpc_adam_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
-                  self.wd, self.dev_bc, grad_scale)
-
     def _baked_scalars(self) -> tuple:
         """host scalars a captured step carries as kernel arguments (a replay keeps the values of its capture)"""
-        gd = getattr(self, "gru_desc", None)
-        return (float(self.lr), float(self.wd), float(gd.p_drop) if gd is not None else 0.0, int(gd.seed) if gd is not None else 0)
+        gd = self.gru_desc
+        return (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
 
     def check_graph_capture(self):
         """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
         if self.device.type != "cuda":
             raise L.DpcError("hipGraph capture needs the HIP device")
 
-    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
-        """Captures the whole train step on `block` (a static device buffer: refill it in place between replays) into
-        hipGraphs and returns ``replay() -> device f32[4]``.  One graph without data parallelism; with the two-bucket
-        gradient exchange the capture is cut where the backward hands the gradient tail to RCCL, so the replay is
-        graph A (forward, loss, backward down to layer2) -> all-reduce(tail) asynchronously -> graph B (layer1 + stem
-        backward) -> all-reduce(head) + join -> graph C (Adam).  Dropout masks and Adam's bias corrections are keyed on
-        the device-side step counter, so every replay is a new optimizer step (SURVEY.md section 7 H7/H8).
-        block=None: the step starts from the stem's operand as it stands (train_step(None)): filled in the graph by
-        ``refill=lambda: eng.fill_synthetic(seed)``, or eagerly before each replay (load_recipe)."""
+    def _capture(self, key: tuple, what: str, again: str, warm, body, run, refill=None, **attrs):
+        """what capture_train_step and capture_eval_step share: the cache by `key`, the eager `warm()` and the capture of
+        `body(cut)` on a side stream -- `cut()` ends one graph and begins the next where a replay has host work to do between
+        them --, the fork / join events, and ``replay()``, which checks the baked scalars and returns ``run(engine, graphs)``.
+        `attrs` are hung on the replay closure beside .graphs / .events / .refill."""
         self.check_graph_capture()
-        # every host scalar the capture bakes into kernel arguments is part of the key (dpc_adam_dev takes lr / wd by value, the
-        # recurrence descriptor p_drop / seed): after eng.lr = ... (LR schedule, checkpoint.resume, --reset_lr) asking again captures
-        # a step with the new values instead of handing back the stale replay (ADVICE r5)
-        # refill: optional callable captured in FRONT of the step (e.g. ``lambda: block.normal_()``: a fresh synthetic batch per replay
-        # from torch's graph-safe default generator -- SURVEY section 8d "generated ON DEVICE"); part of the key by identity
-        buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
-        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
-               id(refill) if refill is not None else None) + self._baked_scalars()
         hit = self._captures.get(key)
         if hit is not None:   # the same static buffer, the same exchange: the capture that exists (see _LIVE_GRAPHS)
             return hit
@@ -1290,11 +1287,9 @@ class DPCEngine:
         side = torch.cuda.Stream(self.device)
         side.wait_stream(cur)
         with torch.cuda.stream(side):  # eager warm-up: lazy buffers, RCCL communicator
-            for _ in range(warmup):
-                self.train_step(block, allreduce=allreduce)
+            warm()
         cur.wait_stream(side)
         torch.cuda.synchronize(self.device)
-        two_bucket = allreduce is not None and hasattr(allreduce, "start")
         pool = torch.cuda.graph_pool_handle()
         graphs: List[torch.cuda.CUDAGraph] = []
         state = {}
@@ -1321,31 +1316,69 @@ class DPCEngine:
                 self.packed_for_step = -1
                 if refill is not None:
                     refill()
-                self.forward(block, train=True, materialise=False)
-                self.loss_topk(with_grad=True)
-                self.backward(on_tail_ready=cut if two_bucket else None)
-                if allreduce is not None:
-                    cut()
-                host_steps = self._step_count
-                self.adam_step()
-                self._step_count = host_steps  # capture executes nothing
+                body(cut)
                 state["g"].capture_end()
                 graphs.append(state["g"])
         finally:
             events, self._capture_events = self._capture_events, None
         self.packed_for_step = -1   # the capture executed nothing: the packed weights are not those of this step yet
         cur.wait_stream(side)
-        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:self.grad_split], self.flat_g, self.result
         me = weakref.ref(self)   # the cached closure must not keep its engine (tens of GB of buffers) alive through a cycle
         baked = self._baked_scalars()
 
         def replay():
             eng = me()
             if eng is None:
-                raise RuntimeError("replay of a captured train step whose engine is gone")
+                raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
             if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
                 raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
-                                   "call capture_train_step() again (it captures a new step for the new values)")
+                                   f"call {again}")
+            return run(eng, graphs)
+
+        replay.graphs = graphs
+        replay.events = events   # destroyed after the graphs, not before
+        replay.refill = refill
+        for k, v in attrs.items():
+            setattr(replay, k, v)
+        self._captures[key] = replay
+        self._capture_graphs.append(_Capture(graphs, events))
+        return replay
+
+    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
+        """Captures the whole train step on `block` (a static device buffer: refill it in place between replays) into
+        hipGraphs and returns ``replay() -> device f32[4]``.  One graph without data parallelism; with the two-bucket
+        gradient exchange the capture is cut where the backward hands the gradient tail to RCCL, so the replay is
+        graph A (forward, loss, backward down to layer2) -> all-reduce(tail) asynchronously -> graph B (layer1 + stem
+        backward) -> all-reduce(head) + join -> graph C (Adam).  Dropout masks and Adam's bias corrections are keyed on
+        the device-side step counter, so every replay is a new optimizer step (SURVEY.md section 7 H7/H8).
+        block=None: the step starts from the stem's operand as it stands (train_step(None)): filled in the graph by
+        ``refill=lambda: eng.fill_synthetic(seed)``, or eagerly before each replay (load_recipe)."""
+        # every host scalar the capture bakes into kernel arguments is part of the key (dpc_adam_dev takes lr / wd by value, the
+        # recurrence descriptor p_drop / seed): after eng.lr = ... (LR schedule, checkpoint.resume, --reset_lr) asking again captures
+        # a step with the new values instead of handing back the stale replay (ADVICE r5)
+        # refill: optional callable captured in FRONT of the step (e.g. ``lambda: block.normal_()``: a fresh synthetic batch per replay
+        # from torch's graph-safe default generator -- SURVEY section 8d "generated ON DEVICE"); part of the key by identity
+        buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
+        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
+               id(refill) if refill is not None else None) + self._baked_scalars()
+        two_bucket = allreduce is not None and hasattr(allreduce, "start")
+        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:self.grad_split], self.flat_g, self.result
+
+        def warm():
+            for _ in range(warmup):
+                self.train_step(block, allreduce=allreduce)
+
+        def body(cut):
+            self.forward(block, train=True, materialise=False)
+            self.loss_topk(with_grad=True)
+            self.backward(on_tail_ready=cut if two_bucket else None)
+            if allreduce is not None:
+                cut()
+            host_steps = self._step_count
+            self.adam_step()
+            self._step_count = host_steps  # capture executes nothing
+
+        def run(eng, graphs):
             graphs[0].replay()
             if two_bucket:
                 allreduce.start(tail)
@@ -1359,13 +1392,9 @@ class DPCEngine:
             eng.packed_for_step = -1
             return result
 
-        replay.graphs = graphs
-        replay.events = events   # destroyed after the graphs, not before
-        replay.block = buf   # the static input buffer stays alive (and its address un-reused) as long as the capture does
-        replay.refill = refill
-        self._captures[key] = replay
-        self._capture_graphs.append(_Capture(graphs, events))
-        return replay
+        # block=buf: the static input buffer stays alive (and its address un-reused) as long as the capture does
+        return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
+                             refill, block=buf)
 
     def capture_eval_step(self, refill=None):
         """Captures one validation step on the stem's operand -- `refill` (e.g. ``lambda: eng.fill_synthetic(seed)``), then
@@ -1374,53 +1403,22 @@ class DPCEngine:
         evaluates the weights of now, not those of the capture.  Same rules as capture_train_step: the baked host scalars are part
         of the cache key, the graph is parked (_LIVE_GRAPHS), never destroyed while the process runs.  No eager warm-up: run one
         eager validation step first (the forward allocates its ReLU masks on first use)."""
-        self.check_graph_capture()
         key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
-        hit = self._captures.get(key)
-        if hit is not None:
-            return hit
-        if self._pack_table is None:
-            self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
-        cur = torch.cuda.current_stream(self.device)
-        side = torch.cuda.Stream(self.device)
-        torch.cuda.synchronize(self.device)
-        side.wait_stream(cur)
-        g = torch.cuda.CUDAGraph()
-        keep_events = os.environ.get("DPC_KEEP_CAPTURE_EVENTS", "1") != "0"   # (see capture_train_step)
-        self._capture_events = [] if keep_events else None
-        try:
-            with torch.cuda.stream(side):
-                g.capture_begin(pool=torch.cuda.graph_pool_handle())
-                self.packed_for_step = -1
-                if refill is not None:
-                    refill()
-                self.forward(None, train=False, materialise=False)
-                self.loss_topk(with_grad=False)
-                g.capture_end()
-        finally:
-            events, self._capture_events = self._capture_events, None
-        self.packed_for_step = -1   # the capture executed nothing
-        cur.wait_stream(side)
-        graphs, result = [g], self.result
-        me = weakref.ref(self)
-        baked = self._baked_scalars()
+        result = self.result
 
-        def replay():
-            eng = me()
-            if eng is None:
-                raise RuntimeError("replay of a captured evaluation step whose engine is gone")
-            if eng._baked_scalars() != baked:
-                raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
-                                   "call capture_eval_step() again")
+        def warm():
+            if self._pack_table is None:
+                self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
+
+        def body(cut):
+            self.forward(None, train=False, materialise=False)
+            self.loss_topk(with_grad=False)
+
+        def run(eng, graphs):
             graphs[0].replay()
             return result
 
-        replay.graphs = graphs
-        replay.events = events
-        replay.refill = refill
-        self._captures[key] = replay
-        self._capture_graphs.append(_Capture(graphs, events))
-        return replay
+        return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
 
     def release_captures(self):
         """forget this engine's captured train steps (the next capture_train_step captures again).  The hipGraphs are parked until the
@@ -1435,12 +1433,6 @@ class DPCEngine:
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""
         self.forward(block, train=True, dropout_masks=dropout_masks, materialise=False)
         res = self.loss_topk(with_grad=True)
-        if allreduce is not None and hasattr(allreduce, "start"):
-            self.backward(on_tail_ready=allreduce.start)
-            allreduce.finish(self.flat_g[:self.grad_split])
-        else:
-            self.backward()
-            if allreduce is not None:
-                allreduce(self.flat_g)
+        self._backward_and_exchange(allreduce)
         self.adam_step()
         return res

@@ -16,14 +16,14 @@ state_dict keys (running buffers included), so ``--pretrain`` of a DPC checkpoin
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .engine import BN_EPS, DPCEngine, LAYER_PLAN, LAYER_WIDTH, param_shapes
+from .engine import BN_EPS, BackboneEngine, LAYER_WIDTH, param_shapes
+from .model import _REPLICA_ERROR, _EngineModule, _attach, _init_reference_style
 
 
 def lc_param_shapes(network: str, num_class: int, widths: Sequence[int] = LAYER_WIDTH) -> "Dict[str, Tuple[int, ...]]":
@@ -55,9 +55,8 @@ def lc_state_dict_keys(network: str, num_class: int, widths: Sequence[int] = LAY
     return keys
 
 
-class LCEngine(DPCEngine):
+class LCEngine(BackboneEngine):
     """forward / loss / backward / Adam of the LC classifier as fixed kernel sequences (no autograd graph)"""
-    BN_RUNNING = True
 
     def __init__(self, network: str = "resnet18", sample_size: int = 128, num_seq: int = 8, seq_len: int = 5, batch: int = 4,
                  device="cuda", compute_dtype=torch.float32, widths: Sequence[int] = LAYER_WIDTH, lib: Optional[L.Lib] = None,
@@ -65,40 +64,18 @@ class LCEngine(DPCEngine):
                  seed: int = 666):
         self.num_class = int(num_class)
         self.p_drop_fc = float(dropout)
-        super().__init__(network, sample_size, num_seq, seq_len, 0, batch, device, compute_dtype, widths, lib, lr, wd, gru_dropout,
-                         seed, score_path="materialised")
-
-    def _param_shapes(self):
-        return lc_param_shapes(self.network, self.num_class, self.widths)
+        super().__init__(lc_param_shapes(network, self.num_class, widths), network, sample_size, num_seq, seq_len, batch, device,
+                         compute_dtype, widths, lib, lr, wd, gru_dropout, seed, bn_running=True)
+        self._build_head()
+        self._finish_buffers()
 
     # ---- head: ConvGRU over all N blocks (P = 0) + BatchNorm1d / Dropout / Linear / CE
     def _build_head(self):
         B, N, SQ, D, dt, NC = self.B, self.N, self.SQ, self.D, self.cdtype, self.num_class
         f32 = torch.float32
-        if D % 32 or D > 256:
-            raise ValueError("feature size must be a multiple of 32, at most 256 (fused ConvGRU recurrence)")
-        M = B * SQ
-        self.M, self.n_agg, self.n_steps = M, N, N
-        self.feat_relu = self.empty((N, M, D), dt)
-        self.X_all = self.feat_relu
-        self.H_all = torch.zeros((N + 1, M, D), dtype=dt, device=self.device)
-        self.HR_all = self.empty((N, M, D), dt)
-        self.G_all = self.empty((N, M, 3 * D), dt)
-        self.U_all, self.R_all, self.O_all = (self.empty((N, M, D), f32) for _ in range(3))
-        self.d_featrelu = self.empty((N, M, D), f32)
-        self.d_feat = self.empty(self.feat_shape + (D,), dt)
+        self._build_gru(n_agg=N, n_steps=N, P=0)
+        M = self.M
         self.d_hlast = self.empty((M, D), f32)
-        self.gru_packed = self.empty((16 * D * D,), dt)
-        self.gru_ws = self.empty((2, M, D), f32)
-        self.dev_step = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.dev_bc = torch.ones(2, dtype=f32, device=self.device)
-        self.dev_draw = torch.zeros(1, dtype=torch.int32, device=self.device)  # dropout draw counter (one per train-mode forward)
-        self.drop_all = None
-        self.dWx, self.dWh, self.dWo = self.empty((3 * D, D), f32), self.empty((2 * D, D), f32), self.empty((D, D), f32)
-        self.db = self.empty((3 * D,), f32)
-        for (co, kk) in ((3 * D, D), (2 * D, D), (D, D)):
-            self._need_wgrad(N * M, co, kk)
-        self.need_part(64 * 3 * D)
         self.BUF["final_bn.running_mean"] = torch.zeros(D, dtype=f32, device=self.device)
         self.BUF["final_bn.running_var"] = torch.ones(D, dtype=f32, device=self.device)
         self.BUF["final_bn.num_batches_tracked"] = torch.zeros((), dtype=torch.int64, device=self.device)
@@ -107,16 +84,9 @@ class LCEngine(DPCEngine):
         self.bn1d_stat = self.empty((2, D), f32)
         self.logits, self.dlogits = self.empty((B, NC), f32), self.empty((B, NC), f32)
         self.row_ws, self.result = self.empty((B, 2), f32), self.empty((2,), f32)
-        Pm = self.PRM
-        gd = self.gru_desc = L.GruChainDesc()
-        gd.dtype, gd.M, gd.D, gd.SQ, gd.P, gd.n_agg, gd.n_steps = L.dtype_code(dt), M, D, SQ, 0, N, N
-        gd.p_drop, gd.seed = float(self.p_drop), self.seed
-        for name, t in (("packed", self.gru_packed), ("bias_u", Pm["agg.ConvGRUCell_00.update_gate.bias"]),
-                        ("bias_r", Pm["agg.ConvGRUCell_00.reset_gate.bias"]), ("bias_o", Pm["agg.ConvGRUCell_00.out_gate.bias"]),
-                        ("bias_1", Pm["agg.ConvGRUCell_00.out_gate.bias"]), ("bias_2", Pm["agg.ConvGRUCell_00.out_gate.bias"]),  # unused (P = 0)
-                        ("X_all", self.X_all), ("H_all", self.H_all), ("HR_all", self.HR_all), ("U_all", self.U_all),
-                        ("R_all", self.R_all), ("O_all", self.O_all), ("G_all", self.G_all), ("d_x", self.d_featrelu),
-                        ("ws", self.gru_ws), ("d_hlast", self.d_hlast)):
+        Pm, gd = self.PRM, self.gru_desc
+        for name, t in (("bias_1", Pm["agg.ConvGRUCell_00.out_gate.bias"]), ("bias_2", Pm["agg.ConvGRUCell_00.out_gate.bias"]),  # unused (P = 0)
+                        ("d_hlast", self.d_hlast)):
             setattr(gd, name, t.data_ptr())
         hd = self.head_desc = L.LcHeadDesc()
         hd.dtype, hd.B, hd.SQ, hd.D, hd.num_class, hd.train = L.dtype_code(dt), B, SQ, D, NC, 1
@@ -190,33 +160,18 @@ class LCEngine(DPCEngine):
         """gradients of the mean CE loss of the last train-mode forward w.r.t. every parameter"""
         if not self.train_mode:
             raise L.DpcError("LCEngine.backward needs a train-mode forward (BatchNorm with batch statistics)")
-        B, N, SQ, D, M = self.B, self.N, self.SQ, self.D, self.M
+        B, N, SQ, D = self.B, self.N, self.SQ, self.D
         dc = L.dtype_code(self.cdtype)
         self.call("dpc_lc_head_bwd", C.byref(self.head_desc))
         self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
-        Gm = self.G
-        self.gemm_tn(self.G_all, 3 * D, self.X_all, D, self.dWx, N * M, 3 * D, D)
-        self.gemm_tn(self.G_all, 3 * D, self.H_all, D, self.dWh, N * M, 2 * D, D)
-        self.gemm_tn(self.G_all[:, :, 2 * D:], 3 * D, self.HR_all, D, self.dWo, N * M, D, D)
-        self.call("dpc_colsum", self.G_all, dc, 3 * D, N * M, 3 * D, self.db, 0, self.part, self.part.numel())
-        for i, (g, n) in enumerate((("u", "update_gate"), ("r", "reset_gate"), ("o", "out_gate"))):
-            w = Gm[f"agg.ConvGRUCell_00.{n}.weight"].view(D, 2 * D)
-            self.call("dpc_copy2d_f32", self.dWx[i * D:(i + 1) * D], D, w, 2 * D, D, D)
-            self.call("dpc_copy2d_f32", self.dWh[i * D:(i + 1) * D] if g != "o" else self.dWo, D, w[:, D:], 2 * D, D, D)
-            self.call("dpc_copy2d_f32", self.db[i * D:(i + 1) * D], D, Gm[f"agg.ConvGRUCell_00.{n}.bias"], D, 1, D)
+        self._gru_param_grads(dc)
         self.call("dpc_relu_tpool_bwd", self.blocks[-1].out, self.d_featrelu, dc, B, N, self.feat_shape[1], SQ, D, self.d_feat)
         self._backbone_backward(self.d_feat, on_tail_ready)
 
     def train_step(self, block: torch.Tensor, target: torch.Tensor, allreduce=None, **masks) -> torch.Tensor:
         """forward + CE / accuracy + backward (+ gradient all-reduce) + Adam; returns device f32[2] = loss, top-1"""
         self.forward(block, target, train=True, **masks)
-        if allreduce is not None and hasattr(allreduce, "start"):
-            self.backward(on_tail_ready=allreduce.start)
-            allreduce.finish(self.flat_g[:self.grad_split])
-        else:
-            self.backward()
-            if allreduce is not None:
-                allreduce(self.flat_g)
+        self._backward_and_exchange(allreduce)
         self.adam_step()
         return self.result
 
@@ -263,136 +218,33 @@ class LCEngine(DPCEngine):
         self.call("dpc_lc_test_finish", self.test_psum, self.test_lsum, self.test_count, self.num_class, label, self.test_prob, self.test_res,
                   self.test_totals, self.test_confusion)
 
-    # the DPC-specific entry points do not exist on this engine
-    def loss_topk(self, with_grad: bool = True):
-        return self.result
 
-    def capture_train_step(self, *a, **k):
-        raise NotImplementedError("hipGraph capture is wired for the DPC-RNN step only")
-
-    def get_mask(self):
-        raise AttributeError("LC has no contrastive mask")
-
-
-class _Holder(nn.Module):
-    """namespace module so that parameters / buffers appear under the reference's dotted names"""
-
-
-def _attach(root: nn.Module, dotted: str, value, buffer: bool):
-    parts = dotted.split(".")
-    mod = root
-    for p in parts[:-1]:
-        if not hasattr(mod, p):
-            setattr(mod, p, _Holder())
-        mod = getattr(mod, p)
-    if buffer:
-        mod.register_buffer(parts[-1], value)
-    else:
-        mod.register_parameter(parts[-1], value)
-
-
-class LC(nn.Module):
+class LC(_EngineModule):
     """drop-in for eval/model_3d_lc.py:12: ``LC(sample_size, num_seq, seq_len, network, dropout, num_class)``,
     ``forward(block) -> (output [B,1,num_class], context [B,1,D])``.  Inference and the engine's own train step are the
     supported uses (``engine.train_step(block, target)``); torch autograd through forward is not wired for this head."""
+    _SAVED_AS = "eval/test.py:205-214"
 
     def __init__(self, sample_size, num_seq, seq_len, network="resnet18", dropout=0.5, num_class=101,
                  compute_dtype=torch.float32, widths=LAYER_WIDTH, seed: int = 0, _simulator: Optional[L.Lib] = None):
-        super().__init__()
-        if network not in LAYER_PLAN:
-            raise IOError("model type is wrong")
-        self.sample_size, self.num_seq, self.seq_len, self.num_class = sample_size, num_seq, seq_len, num_class
-        self.network, self.dropout, self.compute_dtype, self.widths = network, dropout, compute_dtype, tuple(widths)
-        self.last_duration = int(math.ceil(seq_len / 4))
-        self.last_size = int(math.ceil(sample_size / 32))
-        self.param = {"feature_size": widths[3], "num_layers": 1, "hidden_size": widths[3]}
-        self._simulator, self._engine, self._engine_key = _simulator, None, None
-        g = torch.Generator().manual_seed(seed)
+        super().__init__(sample_size, num_seq, seq_len, network, compute_dtype, widths, _simulator)
+        self.num_class, self.dropout = num_class, dropout
         shapes = lc_param_shapes(network, num_class, widths)
+        init = _init_reference_style(shapes, torch.Generator().manual_seed(seed))
         for k in lc_state_dict_keys(network, num_class, widths):
             if k.startswith("agg.cell_list.0."):
                 continue
             if k in shapes:
-                shp = shapes[k]
-                if k.startswith("backbone") and len(shp) == 5:   # kaiming_normal(fan_out), resnet_2d3d.py:224-230
-                    v = torch.randn(shp, generator=g) * math.sqrt(2.0 / (shp[0] * shp[2] * shp[3] * shp[4]))
-                elif k.startswith("backbone") or k.startswith("final_bn"):
-                    v = torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
-                elif k.endswith("bias"):
-                    v = torch.zeros(shp)
-                else:                                              # orthogonal gain 1 (model_3d_lc.py:67-72)
-                    v = torch.empty(shp)
-                    nn.init.orthogonal_(v, 1, generator=g)
-                _attach(self, k, nn.Parameter(v), buffer=False)
+                _attach(self, k, nn.Parameter(init[k]))
             else:
                 C_ = shapes[k.rsplit(".", 1)[0] + ".weight"][0]
                 v = torch.zeros(C_) if k.endswith("running_mean") else (torch.ones(C_) if k.endswith("running_var") else torch.zeros((), dtype=torch.int64))
                 _attach(self, k, v, buffer=True)
         self.agg.cell_list = nn.ModuleList([self.agg.ConvGRUCell_00])
 
-    def _ensure_engine(self, block):
-        """Parameters and BatchNorm buffers of the module ARE the engine's arenas (as in DPC_RNN): ``load_state_dict`` / an
-        optimizer writing through them reach the kernels, and what ``engine.train_step`` / a train-mode forward update (weights,
-        running statistics, num_batches_tracked) is what ``state_dict()`` returns."""
-        key = (block.shape[0], block.device, self.compute_dtype)
-        first = self.backbone.conv1.weight
-        if self._engine is not None and self._engine_key == key and first.data_ptr() == self._engine.PRM["backbone.conv1.weight"].data_ptr():
-            return
-        named = dict(self.named_parameters())
-        bad = [k for k, v in named.items() if v.dtype != torch.float32]
-        if bad:   # .half() / .double() cast the Parameters themselves; the arena holds f32 master weights (as dpc_amd.DPC_RNN)
-            raise TypeError(f"dpc_amd.LC keeps float32 master parameters; {bad[0]} is {named[bad[0]].dtype}.  Select the kernels' operand "
-                            "type with model.bfloat16() / model.float(); .half() and .double() are not supported")
-        eng = LCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, block.shape[0], block.device, self.compute_dtype,
-                       self.widths, self._simulator, dropout=self.dropout, num_class=self.num_class)
-        eng.load_params({k: v.detach() for k, v in self.state_dict().items()})
-        if self._engine is not None:
-            # a rebuild (another batch size, model.bfloat16() after training started, a device move) continues the SAME optimisation:
-            # Adam moments, step counter, bias corrections, dropout draw counter, lr / wd (ADVICE r5; DPC_RNN._ensure_engine does the same)
-            eng.adopt_optimizer_state(self._engine)
-            eng.train_mode = self._engine.train_mode
-        for k, t in eng.PRM.items():
-            named[k].data = t  # re-point the Parameter at its slice of the flat arena
-        for k, t in eng.BUF.items():
-            mod = self
-            *path, leaf = k.split(".")
-            for p_ in path:
-                mod = getattr(mod, p_)
-            mod._buffers[leaf] = t  # same tensor object the kernels update
-        self._engine, self._engine_key = eng, key
-
-    @property
-    def engine(self) -> Optional[LCEngine]:
-        return self._engine
-
-    # ---- compute dtype through the calls a user of the reference would make (as dpc_amd.DPC_RNN): parameters stay f32
-    def bfloat16(self):
-        self.compute_dtype = torch.bfloat16
-        return self
-
-    def float(self):
-        self.compute_dtype = torch.float32
-        return self
-
-    def half(self):
-        raise TypeError("dpc_amd.LC: fp16 is not a mode of this build (bf16 operands with f32 accumulation and f32 master weights are: model.bfloat16())")
-
-    def double(self):
-        raise TypeError("dpc_amd.LC: parameters are float32 master weights; there is no f64 mode")
-
-    def to(self, *args, **kwargs):
-        """device moves as nn.Module.to; an explicit floating dtype selects the compute dtype instead of casting the master parameters"""
-        dtype = kwargs.get("dtype")
-        rest = [a for a in args if not isinstance(a, torch.dtype)]
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-        if dtype is not None:
-            if dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"dpc_amd.LC.to({dtype}): compute dtypes are torch.float32 and torch.bfloat16")
-            self.compute_dtype = dtype
-        kw = {k: v for k, v in kwargs.items() if k != "dtype"}
-        return super().to(*rest, **kw) if (rest or kw) else self
+    def _make_engine(self, B, dev):
+        return LCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, B, dev, self.compute_dtype,
+                        self.widths, self._simulator, dropout=self.dropout, num_class=self.num_class)
 
     def __deepcopy__(self, memo):
         """a fresh module with the same constructor arguments, cloned parameter / buffer values and no engine (as DPC_RNN.__deepcopy__)"""
@@ -406,13 +258,8 @@ class LC(nn.Module):
         memo[id(self)] = new
         return new
 
-    def __reduce_ex__(self, protocol):
-        raise TypeError("dpc_amd.LC is not picklable as a whole (its engine owns device buffers): save model.state_dict() as "
-                        "eval/test.py:205-214 does")
-
     def forward(self, block, target: Optional[torch.Tensor] = None):
         if getattr(self, "_is_replica", False):   # nn.DataParallel over several devices (eval/test.py:63): see dpc_amd.model._REPLICA_ERROR
-            from .model import _REPLICA_ERROR
             raise RuntimeError(_REPLICA_ERROR.replace("dpc_amd.DPC_RNN", "dpc_amd.LC").replace("dpc_amd.main", "dpc_amd.lc_main").replace("dpc/main.py", "eval/test.py"))
         if block.device.type != "cuda" and self._simulator is None:
             raise L.DpcError("dpc_amd.LC runs on MI355X only: move the module and the input to a cuda (HIP) device")

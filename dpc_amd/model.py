@@ -62,28 +62,31 @@ _REPLICA_ERROR = ("dpc_amd.DPC_RNN cannot run as an nn.DataParallel replica (Dat
 
 
 class _Holder(nn.Module):
-    """namespace module so that parameters appear under the reference's dotted names"""
+    """namespace module so that parameters / buffers appear under the reference's dotted names"""
 
 
-def _attach(root: nn.Module, dotted: str, param: nn.Parameter):
+def _attach(root: nn.Module, dotted: str, value, buffer: bool = False):
     parts = dotted.split(".")
     mod = root
     for p in parts[:-1]:
         if not hasattr(mod, p):
             setattr(mod, p, _Holder())
         mod = getattr(mod, p)
-    mod.register_parameter(parts[-1], param)
+    if buffer:
+        mod.register_buffer(parts[-1], value)
+    else:
+        mod.register_parameter(parts[-1], value)
 
 
 def _init_reference_style(shapes: Dict[str, tuple], gen: torch.Generator) -> Dict[str, torch.Tensor]:
-    """kaiming_normal(fan_out) convs + BN 1/0 (backbone/resnet_2d3d.py:224-230); orthogonal gain 1,
-    zero bias for agg / network_pred (dpc/model_3d.py:100-106)."""
+    """kaiming_normal(fan_out) convs + BN 1/0 (backbone/resnet_2d3d.py:224-230, LC's final_bn); orthogonal gain 1,
+    zero bias for agg / network_pred / final_fc (dpc/model_3d.py:100-106, eval/model_3d_lc.py:67-72)."""
     out = {}
     for k, shp in shapes.items():
         if k.startswith("backbone") and len(shp) == 5:
             fan_out = shp[0] * shp[2] * shp[3] * shp[4]
             out[k] = torch.randn(shp, generator=gen) * math.sqrt(2.0 / fan_out)
-        elif k.startswith("backbone"):
+        elif k.startswith("backbone") or k.startswith("final_bn"):
             out[k] = torch.ones(shp) if k.endswith("weight") else torch.zeros(shp)
         elif k.endswith("bias"):
             out[k] = torch.zeros(shp)
@@ -92,6 +95,101 @@ def _init_reference_style(shapes: Dict[str, tuple], gen: torch.Generator) -> Dic
             nn.init.orthogonal_(w, 1, generator=gen)
             out[k] = w
     return out
+
+
+class _EngineModule(nn.Module):
+    """What the drop-in modules (DPC_RNN here, lc.LC) share: the reference's public attributes, the engine lifecycle -- Parameters
+    and BatchNorm buffers of the module ARE the engine's arenas, so ``load_state_dict`` / an optimizer writing through them reach
+    the kernels and what the engine updates is what ``state_dict()`` returns -- and the compute-dtype calls.  A subclass gives
+    ``_make_engine(batch, device)`` and ``_SAVED_AS``, where the reference saves what cannot be pickled here."""
+    _SAVED_AS = ""
+
+    def __init__(self, sample_size, num_seq, seq_len, network, compute_dtype, widths, _simulator):
+        super().__init__()
+        if network not in LAYER_PLAN:
+            raise IOError("model type is wrong")  # select_backbone.py:19 (resnet50+ are outside this build's scope)
+        self.sample_size, self.num_seq, self.seq_len, self.network = sample_size, num_seq, seq_len, network
+        self.last_duration = int(math.ceil(seq_len / 4))
+        self.last_size = int(math.ceil(sample_size / 32))
+        self.param = {"feature_size": widths[3], "num_layers": 1, "hidden_size": widths[3]}
+        self.compute_dtype = compute_dtype
+        self.widths = tuple(widths)
+        self._simulator = _simulator  # tests only: the host-side SIMT simulator handle (CPU tier); never set by the product
+        self._engine, self._engine_key = None, None
+
+    # ---- engine lifecycle: parameters live in the engine's flat arena on the current device
+    def _ensure_engine(self, block: torch.Tensor):
+        key = (block.shape[0], block.device, self.compute_dtype)
+        first = self.backbone.conv1.weight
+        if self._engine is not None and self._engine_key == key and first.data_ptr() == self._engine.PRM["backbone.conv1.weight"].data_ptr():
+            return
+        named = dict(self.named_parameters())
+        bad = [k for k, v in named.items() if v.dtype != torch.float32]
+        if bad:   # .half() / .double() / .to(torch.bfloat16) cast the Parameters themselves; the arena holds f32 master weights
+            raise TypeError(f"dpc_amd.{type(self).__name__} keeps float32 master parameters (the reference's state_dict dtype); {bad[0]} "
+                            f"is {named[bad[0]].dtype}.  Select the kernels' operand type with model.bfloat16() / model.float(); "
+                            ".half() and .double() are not supported")
+        eng = self._make_engine(block.shape[0], block.device)
+        eng.load_params({k: v.detach() for k, v in self.state_dict().items()})
+        if self._engine is not None:
+            # a rebuild (another batch size, model.bfloat16() after training started, a device move) continues the SAME optimisation:
+            # Adam moments, step counter / bias corrections and the dropout draw counter move over, as they would stay put under
+            # torch.optim.Adam, whose state is keyed on the Parameter objects and survives all three (ADVICE r4)
+            eng.adopt_optimizer_state(self._engine)
+            eng.train_mode = self._engine.train_mode
+        for k, t in eng.PRM.items():
+            named[k].data = t  # re-point the Parameter at its slice of the flat arena
+        for k, t in eng.BUF.items():
+            *path, leaf = k.split(".")
+            mod = self
+            for p_ in path:
+                mod = getattr(mod, p_)
+            mod._buffers[leaf] = t  # same tensor object the kernels update
+        self._engine, self._engine_key = eng, key
+
+    @property
+    def engine(self):
+        return self._engine
+
+    # ---- compute dtype through the calls a user of the reference would make.  Parameters stay f32 (master weights of the
+    # fused Adam, the reference's state_dict dtype); only the kernels' operand type changes, and the engine is rebuilt at the
+    # next forward.  model.bfloat16() = throughput mode (BASELINE configs[1]), model.float() = the 1e-3 parity mode.
+    def bfloat16(self):
+        self.compute_dtype = torch.bfloat16
+        return self
+
+    def float(self):
+        self.compute_dtype = torch.float32
+        return self
+
+    def half(self):
+        raise TypeError(f"dpc_amd.{type(self).__name__}: fp16 is not a mode of this build (bf16 operands with f32 accumulation and f32 "
+                        "master weights are: model.bfloat16())")
+
+    def double(self):
+        raise TypeError(f"dpc_amd.{type(self).__name__}: parameters are float32 master weights; there is no f64 mode")
+
+    def to(self, *args, **kwargs):
+        """device moves as nn.Module.to; a floating dtype selects the compute dtype like .bfloat16() / .float() instead of casting
+        the f32 master parameters (model.to(torch.bfloat16) == model.bfloat16())"""
+        dtype = kwargs.get("dtype")          # only an EXPLICIT dtype argument is a compute-dtype selection; everything else
+        rest = [a for a in args if not isinstance(a, torch.dtype)]   # (device, tensor, memory_format, non_blocking) goes to nn.Module.to
+        for a in args:
+            if isinstance(a, torch.dtype):
+                dtype = a
+        if dtype is not None:
+            if dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError(f"dpc_amd.{type(self).__name__}.to({dtype}): compute dtypes are torch.float32 and torch.bfloat16")
+            self.compute_dtype = dtype
+        kw = {k: v for k, v in kwargs.items() if k != "dtype"}
+        if rest and isinstance(rest[0], torch.Tensor):   # model.to(tensor): its device only, never its dtype
+            rest[0] = rest[0].device
+        return super().to(*rest, **kw) if (rest or kw) else self
+
+    # The engine holds device buffers, ctypes descriptors and captured graphs: none of that is copied or pickled.
+    def __reduce_ex__(self, protocol):
+        raise TypeError(f"dpc_amd.{type(self).__name__} is not picklable as a whole (its engine owns device buffers and captured "
+                        f"graphs): save model.state_dict() as {self._SAVED_AS} does")
 
 
 class _DPCScore(torch.autograd.Function):
@@ -165,28 +263,18 @@ class _DPCScoreReplica(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(eng.G[k] for k in ctx.names)
 
 
-class DPC_RNN(nn.Module):
+class DPC_RNN(_EngineModule):
     """DPC with RNN (dpc/model_3d.py:14)"""
+    _SAVED_AS = "dpc/main.py:166-174 (dpc_amd.checkpoint writes the reference's dictionary)"
 
     def __init__(self, sample_size, num_seq=8, seq_len=5, pred_step=3, network="resnet50",
                  compute_dtype=torch.float32, widths=LAYER_WIDTH, seed: int = 0, _simulator: Optional[L.Lib] = None):
-        super().__init__()
-        if network not in LAYER_PLAN:
-            raise IOError("model type is wrong")  # select_backbone.py:19 (resnet50+ are outside this build's scope)
-        self.sample_size, self.num_seq, self.seq_len, self.pred_step = sample_size, num_seq, seq_len, pred_step
-        self.network = network
-        self.last_duration = int(math.ceil(seq_len / 4))
-        self.last_size = int(math.ceil(sample_size / 32))
-        self.param = {"feature_size": widths[3], "num_layers": 1, "hidden_size": widths[3]}
-        self.compute_dtype = compute_dtype
-        self.widths = tuple(widths)
+        super().__init__(sample_size, num_seq, seq_len, network, compute_dtype, widths, _simulator)
+        self.pred_step = pred_step
         self.mask = None
-        self._engine: Optional[DPCEngine] = None
-        self._engine_key = None
         self._param_names: List[str] = []
         self._forced_masks = None
         self._fwd_generation = 0
-        self._simulator = _simulator  # tests only: the host-side SIMT simulator handle (CPU tier); never set by the product
         self._score_bufs = None
         # engines of nn.DataParallel replicas by (device, slot, batch, compute dtype); the dict and its lock are shared with every replica
         # (a replica's __dict__ is a shallow copy of the root's: torch nn/modules/module.py _replicate_for_data_parallel)
@@ -205,32 +293,10 @@ class DPC_RNN(nn.Module):
         # the reference registers the single GRU cell twice (convrnn.py:55-58): alias module, same Parameters
         self.agg.cell_list = nn.ModuleList([self.agg.ConvGRUCell_00])
 
-    # ---- engine lifecycle: parameters live in the engine's flat arena on the current device
-    def _ensure_engine(self, block: torch.Tensor):
-        B = block.shape[0]
-        dev = block.device
-        key = (B, dev, self.compute_dtype)
-        first = self.backbone.conv1.weight
-        if self._engine is not None and self._engine_key == key and first.data_ptr() == self._engine.PRM[self._param_names[0]].data_ptr():
-            return
-        named = {k: v for k, v in self.named_parameters()}
-        bad = [k for k in self._param_names if named[k].dtype != torch.float32]
-        if bad:   # .half() / .double() / .to(torch.bfloat16) cast the Parameters themselves; the arena holds f32 master weights
-            raise TypeError(f"dpc_amd.DPC_RNN keeps float32 master parameters (the reference's state_dict dtype); {bad[0]} is "
-                            f"{named[bad[0]].dtype}.  Select the kernels' operand type with model.bfloat16() / model.float() (or "
-                            "DPC_COMPUTE_DTYPE=bf16|f32); .half() and .double() are not supported")
-        eng = DPCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, self.pred_step, B, dev,
-                        self.compute_dtype, self.widths, lib=self._simulator)
-        eng.load_params({k: named[k].detach() for k in self._param_names})
-        if self._engine is not None:
-            # a rebuild (another batch size, model.bfloat16() after training started, a device move) continues the SAME optimisation:
-            # Adam moments, step counter / bias corrections and the dropout draw counter move over, as they would stay put under
-            # torch.optim.Adam, whose state is keyed on the Parameter objects and survives all three
-            eng.adopt_optimizer_state(self._engine)
-        for k in self._param_names:
-            named[k].data = eng.PRM[k]  # re-point the Parameter at its slice of the flat arena
-        self._engine, self._engine_key = eng, key
-        self.mask = None
+    def _make_engine(self, B, dev):
+        self.mask = None   # the contrastive mask belongs to the engine this one replaces
+        return DPCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, self.pred_step, B, dev,
+                         self.compute_dtype, self.widths, lib=self._simulator)
 
     def forward(self, block):
         # block: [B, N, C, SL, H, W] (dpc/model_3d.py:47-49)
@@ -280,42 +346,7 @@ class DPC_RNN(nn.Module):
     def reset_mask(self):
         self.mask = None
 
-    # ---- compute dtype through the calls a user of the reference would make.  Parameters stay f32 (master weights of the
-    # fused Adam, the reference's state_dict dtype); only the kernels' operand type changes, and the engine is rebuilt at the
-    # next forward.  model.bfloat16() = throughput mode (BASELINE configs[1]), model.float() = the 1e-3 parity mode.
-    def bfloat16(self):
-        self.compute_dtype = torch.bfloat16
-        return self
-
-    def float(self):
-        self.compute_dtype = torch.float32
-        return self
-
-    def half(self):
-        raise TypeError("dpc_amd.DPC_RNN: fp16 is not a mode of this build (bf16 operands with f32 accumulation and f32 master "
-                        "weights are: model.bfloat16())")
-
-    def double(self):
-        raise TypeError("dpc_amd.DPC_RNN: parameters are float32 master weights; there is no f64 mode")
-
-    def to(self, *args, **kwargs):
-        """device moves as nn.Module.to; a floating dtype selects the compute dtype like .bfloat16() / .float() instead of casting
-        the f32 master parameters (model.to(torch.bfloat16) == model.bfloat16())"""
-        dtype = kwargs.get("dtype")          # only an EXPLICIT dtype argument is a compute-dtype selection; everything else
-        rest = [a for a in args if not isinstance(a, torch.dtype)]   # (device, tensor, memory_format, non_blocking) goes to nn.Module.to
-        for a in args:
-            if isinstance(a, torch.dtype):
-                dtype = a
-        if dtype is not None:
-            if dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError(f"dpc_amd.DPC_RNN.to({dtype}): compute dtypes are torch.float32 and torch.bfloat16")
-            self.compute_dtype = dtype
-        kw = {k: v for k, v in kwargs.items() if k != "dtype"}
-        if rest and isinstance(rest[0], torch.Tensor):   # model.to(tensor): its device only, never its dtype
-            rest[0] = rest[0].device
-        return super().to(*rest, **kw) if (rest or kw) else self
-
-    # ---- copies.  The engine holds device buffers, ctypes descriptors and captured graphs: none of that is copied or pickled.
+    # ---- copies: a copy gets no engine and builds its own at its first forward
     def __deepcopy__(self, memo):
         """a fresh module with the same constructor arguments, the same parameter VALUES (clones, not arena views) and no engine --
         it builds its own at its first forward (copy.deepcopy(model): EMA / averaged copies, torch.optim.swa_utils.AveragedModel)"""
@@ -331,15 +362,7 @@ class DPC_RNN(nn.Module):
         memo[id(self)] = new
         return new
 
-    def __reduce_ex__(self, protocol):
-        raise TypeError("dpc_amd.DPC_RNN is not picklable as a whole (its engine owns device buffers and captured graphs): save "
-                        "model.state_dict() as dpc/main.py:166-174 does (dpc_amd.checkpoint writes the reference's dictionary)")
-
     def _score_buffers(self, eng):
         if self._score_bufs is None or self._score_bufs[0].shape != eng.score.shape or self._score_bufs[0].device != eng.score.device:
             self._score_bufs = (eng.score, torch.empty_like(eng.score))
         return self._score_bufs
-
-    @property
-    def engine(self) -> Optional[DPCEngine]:
-        return self._engine

@@ -1,9 +1,10 @@
 """Which gfx950 kernel serves which convolution of the 2d3d-ResNet -- the static schedule's kernel plan, queryable
 without a GPU (``dpc_conv_plan`` runs the library's own dispatch code with the launch skipped, include/dpc_hip.h).
 
-``backbone_units`` walks the reference's layer plan (backbone/resnet_2d3d.py:205-284) exactly as ``DPCEngine`` does and
-``unit_descs`` builds the three descriptors of a Conv3d + BatchNorm3d unit (forward, input-gradient, weight-gradient): the
-engine uses the same function, so the table printed here is what a train step launches.  tests/test_plan.py pins the table
+``walk_blocks`` is the one walk over the reference's layer plan (backbone/resnet_2d3d.py:205-284), ``block_geometry`` the one
+statement of a block's conv geometry and ``fold_decision`` the one decision which backward pieces ride in input-gradient
+epilogues; ``unit_descs`` builds the three descriptors of a Conv3d + BatchNorm3d unit (forward, input-gradient,
+weight-gradient).  The engine builds itself from the same functions, so the table printed here is what a train step launches.  tests/test_plan.py pins the table
 for BASELINE.json's configurations; ``python -m dpc_amd.plan cfg2`` prints it.
 """
 from __future__ import annotations
@@ -40,36 +41,49 @@ def unit_descs(Ci: int, Co: int, k, s, p, in_shape, dtype: torch.dtype, stem: bo
     return desc_f, desc_d, desc_w
 
 
+def walk_blocks(network: str, widths: Sequence[int] = LAYER_WIDTH):
+    """the BasicBlocks of the backbone in forward order (backbone/resnet_2d3d.py:205-257):
+    yields (prefix "layerL.B.", cin, planes, is3d, stride, has_ds, last)"""
+    if network not in LAYER_PLAN:
+        raise IOError("model type is wrong")  # backbone/select_backbone.py:19
+    plan = LAYER_PLAN[network]
+    inplanes = widths[0]
+    for li in range(4):
+        planes = widths[li]
+        for bi in range(plan[li]):
+            stride = 2 if (li > 0 and bi == 0) else 1
+            has_ds = bi == 0 and (stride != 1 or inplanes != planes)
+            yield f"layer{li + 1}.{bi}.", inplanes if bi == 0 else planes, planes, li >= 2, stride, has_ds, li == 3 and bi == plan[li] - 1
+        inplanes = planes
+
+
+def block_geometry(is3d: bool, stride: int):
+    """(k, s, p) of a block's conv1; conv2 is the same at stride 1, the downsample a 1x1x1 conv at s without padding"""
+    k = (3, 3, 3) if is3d else (1, 3, 3)
+    p = (1, 1, 1) if is3d else (0, 1, 1)
+    s = (stride,) * 3 if is3d else (1, stride, stride)
+    return k, s, p
+
+
 def backbone_units(network: str, size: int, batch: int, num_seq: int = 8, seq_len: int = 5,
                    widths: Sequence[int] = LAYER_WIDTH) -> "List[Dict]":
     """every conv unit of the backbone in forward order: name, geometry and how the backward uses its input-gradient"""
-    if network not in LAYER_PLAN:
-        raise IOError("model type is wrong")
     BN, H = batch * num_seq, size
     units = [dict(name="conv1", Ci=16, Co=widths[0], k=(1, 4, 4), s=(1, 1, 1), p=(0, 2, 2), in_shape=(BN, seq_len, H // 2, H // 2),
                   stem=True, dgrad=None)]
     hp = (H // 2 - 1) // 2 + 1
-    shape, inplanes = (BN, seq_len, hp, hp), widths[0]
-    for li in range(4):
-        planes = widths[li]
-        is3d = li >= 2
-        for bi in range(LAYER_PLAN[network][li]):
-            stride = 2 if (li > 0 and bi == 0) else 1
-            has_ds = bi == 0 and (stride != 1 or inplanes != planes)
-            k = (3, 3, 3) if is3d else (1, 3, 3)
-            p = (1, 1, 1) if is3d else (0, 1, 1)
-            s = (stride,) * 3 if is3d else (1, stride, stride)
-            cin = inplanes if bi == 0 else planes
-            pre = f"layer{li + 1}.{bi}."
-            mid = out_shape_of(shape, k, s, p)
-            # c1's input-gradient carries the residual branch as its addend unless a downsample accumulates in place afterwards
-            units.append(dict(name=pre + "conv1", Ci=cin, Co=planes, k=k, s=s, p=p, in_shape=shape, stem=False,
-                              dgrad="plain" if has_ds else "addend"))
-            units.append(dict(name=pre + "conv2", Ci=planes, Co=planes, k=k, s=(1, 1, 1), p=p, in_shape=mid, stem=False, dgrad="plain"))
-            if has_ds:
-                units.append(dict(name=pre + "downsample.0", Ci=cin, Co=planes, k=(1, 1, 1), s=s, p=(0, 0, 0), in_shape=shape,
-                                  stem=False, dgrad="inplace"))
-            shape, inplanes = mid, planes
+    shape = (BN, seq_len, hp, hp)
+    for pre, cin, planes, is3d, stride, has_ds, _ in walk_blocks(network, widths):
+        k, s, p = block_geometry(is3d, stride)
+        mid = out_shape_of(shape, k, s, p)
+        # c1's input-gradient carries the residual branch as its addend unless a downsample accumulates in place afterwards
+        units.append(dict(name=pre + "conv1", Ci=cin, Co=planes, k=k, s=s, p=p, in_shape=shape, stem=False,
+                          dgrad="plain" if has_ds else "addend"))
+        units.append(dict(name=pre + "conv2", Ci=planes, Co=planes, k=k, s=(1, 1, 1), p=p, in_shape=mid, stem=False, dgrad="plain"))
+        if has_ds:
+            units.append(dict(name=pre + "downsample.0", Ci=cin, Co=planes, k=(1, 1, 1), s=s, p=(0, 0, 0), in_shape=shape,
+                              stem=False, dgrad="inplace"))
+        shape = mid
     return units
 
 
@@ -81,30 +95,27 @@ def ex_supported(lib: L.Lib, desc_d, addend: bool, gate: bool, bnred: bool) -> b
     return bool(ex) and (not ex.startswith("igemm_kernel") or plain.startswith("igemm_kernel"))
 
 
+def fold_decision(lib: L.Lib, d1, d2, has_ds: bool, final_relu: bool, has_prev: bool) -> "Tuple[bool, bool, bool]":
+    """which backward pieces of a BasicBlock ride in input-gradient epilogues, from the input-gradient descriptors of its conv1
+    (d1) and conv2 (d2) (dpc_conv_igemm_ex + the plan query):
+    fold_c1   conv2's input-gradient takes bn1's backward reduction;
+    gate      conv1's input-gradient adds the block's incoming gradient gated by the output ReLU mask (no dz tensor);
+    fold_prev ... and takes the backward reduction of the PREVIOUS block's bn2, whose output gradient it writes."""
+    fold_c1 = ex_supported(lib, d2, False, False, True)
+    gate = (not has_ds) and ex_supported(lib, d1, True, final_relu, False)
+    fold_prev = bool(has_prev and gate and ex_supported(lib, d1, True, final_relu, True))
+    return fold_c1, gate, fold_prev
+
+
 def fold_table(lib: L.Lib, network: str, size: int, batch: int, dtype: torch.dtype, **kw) -> "List[Tuple[str, bool, bool, bool]]":
-    """per BasicBlock: (block, fold_c1, gate, fold_prev) as DPCEngine decides them (engine._Block.plan_backward):
-    conv2's input-gradient carries bn1's backward reduction / conv1's input-gradient gates the residual gradient on the fly /
-    ... and carries the previous block's bn2 reduction"""
-    units = backbone_units(network, size, batch, **kw)
-    nblocks = sum(LAYER_PLAN[network])
+    """per BasicBlock: (block, fold_c1, gate, fold_prev) -- fold_decision on the descriptors the engine builds (its own switches,
+    fold=False / DPC_FOLD_RED, come on top there: engine._Block.plan_backward)"""
+    units = {u["name"]: u for u in backbone_units(network, size, batch, **kw)}
     rows = []
-    last = f"layer4.{LAYER_PLAN[network][3] - 1}."
-    first = True
-    for u in units:
-        if not u["name"].endswith("conv1") or u["name"] == "conv1":
-            continue
-        pre = u["name"][:-len("conv1")]
-        c2 = next(v for v in units if v["name"] == pre + "conv2")
-        has_ds = any(v["name"] == pre + "downsample.0" for v in units)
-        final_relu = pre != last
-        d1 = unit_descs(u["Ci"], u["Co"], u["k"], u["s"], u["p"], u["in_shape"], dtype)[1]
-        d2 = unit_descs(c2["Ci"], c2["Co"], c2["k"], c2["s"], c2["p"], c2["in_shape"], dtype)[1]
-        fold_c1 = ex_supported(lib, d2, False, False, True)
-        gate = (not has_ds) and ex_supported(lib, d1, True, final_relu, False)
-        fold_prev = (not first) and gate and ex_supported(lib, d1, True, final_relu, True)
-        rows.append((pre[:-1], fold_c1, gate, fold_prev))
-        first = False
-    assert len(rows) == nblocks
+    for pre, _, _, _, _, has_ds, last in walk_blocks(network, kw.get("widths", LAYER_WIDTH)):
+        d1, d2 = (unit_descs(u["Ci"], u["Co"], u["k"], u["s"], u["p"], u["in_shape"], dtype)[1]
+                  for u in (units[pre + "conv1"], units[pre + "conv2"]))
+        rows.append((pre[:-1],) + fold_decision(lib, d1, d2, has_ds, not last, bool(rows)))
     return rows
 
 

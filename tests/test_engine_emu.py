@@ -152,6 +152,9 @@ def test_fused_backward_epilogues_match_the_separate_kernels(emu):
         assert all(f[0] == fold for f in flags)                                 # conv2's input-gradient always folds bn1
         assert [f[1] for f in flags] == [fold and b.ds is None for b in eng.blocks]   # downsample blocks accumulate in place instead
         assert [f[2] for f in flags] == [fold and b.ds is None and i > 0 for i, b in enumerate(eng.blocks)]
+        if fold:   # the plan query decides as the engine does
+            from dpc_amd import plan
+            assert [r[1:] for r in plan.fold_table(emu, "resnet18", size, B, torch.float32, widths=WIDTHS)] == flags
         eng.forward(x, train=False)
         eng.loss_topk(True)
         eng.backward()
