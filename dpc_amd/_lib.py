@@ -19,6 +19,7 @@ HIP_LIB_PATH = os.path.join(_HERE, "libdpc_hip.so")
 EMU_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tests", "simt_emu", "libdpc_emu.so")
 
 F32, BF16 = 0, 1
+ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3   # DPC_ERR_* (include/dpc_hip.h)
 ABI_VERSION = 1
 
 

@@ -125,8 +125,10 @@ __global__ __launch_bounds__(FIN_THREADS) void bn_finalize_running_kernel(const 
     scale[c] = sc;
     shift[c] = beta[c] - (float)m * sc;
     const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
-    rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)m;
-    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unb;
+    // the momentum update in f64, rounded once: (1 - m) running + m batch cancels where the two differ in sign
+    const double mo = (double)momentum;
+    rmean[c] = (float)((1.0 - mo) * (double)rmean[c] + mo * m);
+    rvar[c] = (float)((1.0 - mo) * (double)rvar[c] + mo * unb);
 }
 
 extern "C" int dpc_bn_finalize_running(const float* partials, int32_t rows, int32_t C, double count, const float* gamma, const float* beta,
@@ -144,12 +146,13 @@ __global__ void bn_eval_coeffs_kernel(const float* gamma, const float* beta, con
                                       float* invstd, float* scale, float* shift) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float is = 1.f / sqrtf(rvar[c] + eps);
+    // f64, each output rounded once: shift = beta - mean * scale cancels where the two are close
+    const double is = 1.0 / sqrt((double)rvar[c] + (double)eps);
+    const double sc = (double)gamma[c] * is;
     mean[c] = rmean[c];
-    invstd[c] = is;
-    const float sc = gamma[c] * is;
-    scale[c] = sc;
-    shift[c] = beta[c] - rmean[c] * sc;
+    invstd[c] = (float)is;
+    scale[c] = (float)sc;
+    shift[c] = (float)((double)beta[c] - (double)rmean[c] * sc);
 }
 
 extern "C" int dpc_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,

@@ -104,6 +104,17 @@ extern "C" int dpc_relu_tpool_bwd(const void* x, const float* d_feat, int32_t dt
 }
 
 // ---------------------------------------------------------------- head forward
+// the Dropout keep value of element o of [B][D], forward and backward alike: the explicit mask, else the Philox draw of the
+// head's own stream, else 1 (eval / p = 0)
+__device__ __forceinline__ float lc_keep(const float* drop, bool philox, unsigned long long seed, uint32_t step, long long o, uint32_t thresh24,
+                                         float inv_keep) {
+    if (drop) return drop[o];
+    if (!philox) return 1.f;
+    float kk[4];
+    dropout_keep4(seed, step, (uint32_t)(o >> 2), thresh24, inv_keep, kk, DPC_PHILOX_STREAM_LC_FC);
+    return kk[o & 3];
+}
+
 // 1. ctx[b][d] = mean_s h[(b,s)][d];  BatchNorm1d over the batch (train: biased batch variance, running buffers updated with
 //    momentum and the unbiased variance; eval: running statistics);  y = bn * dropout mask        (model_3d_lc.py:58-64)
 template <class T>
@@ -114,42 +125,42 @@ __global__ void lc_ctx_bn_kernel(const T* h, int B, int SQ, int D, const float* 
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d == 0 && train && nbt) nbt[0] += 1;
     if (d >= D) return;
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0;
     for (int b = 0; b < B; ++b) {
         float c = 0.f;
         for (int s = 0; s < SQ; ++s) c += Elt<T>::to_f32(h[((long long)b * SQ + s) * D + d]);
         c *= 1.f / (float)SQ;
         ctx[(long long)b * D + d] = c;
-        s1 += c;
-        s2 += c * c;
+        s1 += (double)c;
     }
-    float mean, var;
+    // batch statistics in f64 (as bn.hip's finalize), the variance in a second pass over the ctx column this thread has just
+    // stored: s2/B - mean^2 in f32 loses the variance of a channel whose |mean| >> std (a saturated ConvGRU channel)
+    double mean, var;
     if (train) {
-        mean = s1 / (float)B;
-        var = s2 / (float)B - mean * mean;
-        if (var < 0.f) var = 0.f;
-        const float unb = B > 1 ? var * (float)B / (float)(B - 1) : var;
-        rmean[d] = (1.f - momentum) * rmean[d] + momentum * mean;
-        rvar[d] = (1.f - momentum) * rvar[d] + momentum * unb;
+        mean = s1 / (double)B;
+        double s2 = 0.0;
+        for (int b = 0; b < B; ++b) {
+            const double c = (double)ctx[(long long)b * D + d] - mean;
+            s2 += c * c;
+        }
+        var = s2 / (double)B;
+        if (var < 0.0) var = 0.0;
+        const double unb = B > 1 ? var * (double)B / (double)(B - 1) : var;
+        rmean[d] = (1.f - momentum) * rmean[d] + momentum * (float)mean;
+        rvar[d] = (1.f - momentum) * rvar[d] + momentum * (float)unb;
     } else {
-        mean = rmean[d];
-        var = rvar[d];
+        mean = (double)rmean[d];
+        var = (double)rvar[d];
     }
-    const float is = 1.f / sqrtf(var + eps);
-    stat[d] = mean;
-    stat[D + d] = is;
+    const double is = 1.0 / sqrt(var + (double)eps);
+    stat[d] = (float)mean;
+    stat[D + d] = (float)is;
     const uint32_t step = step_dev ? (uint32_t)step_dev[0] : 0u;
     for (int b = 0; b < B; ++b) {
         const long long o = (long long)b * D + d;
-        const float xh = (ctx[o] - mean) * is;
+        const float xh = (float)(((double)ctx[o] - mean) * is);
         const float bn = xh * gamma[d] + beta[d];
-        float k = 1.f;
-        if (drop) k = drop[o];
-        else if (step_dev) {
-            float kk[4];
-            dropout_keep4(seed, step, (uint32_t)(o >> 2), thresh24, inv_keep, kk, DPC_PHILOX_STREAM_LC_FC);
-            k = kk[o & 3];
-        }
+        const float k = lc_keep(drop, step_dev != nullptr, seed, step, o, thresh24, inv_keep);
         xhat[o] = xh;
         bnout[o] = bn;
         y[o] = bn * k;
@@ -257,18 +268,20 @@ __global__ void lc_fc_wgrad_kernel(const float* dlogits, const float* y, int B, 
 }
 
 // per channel d: dy -> dropout -> BatchNorm1d backward (batch statistics) -> d ctx -> d h_last[(b,s)][d] = d ctx[b][d] / SQ
-__global__ void lc_bn_bwd_kernel(const float* dlogits, const float* W, const float* y, const float* bnout, const float* xhat, const float* stat,
-                                 const float* gamma, int B, int SQ, int D, int NC, float* dgamma, float* dbeta, float* dctx, float* d_hlast) {
+// the keep value comes from where the forward took it (lc_keep), never from y / bn_out: d y / d bn is the keep value whatever bn
+// is, and a channel whose BatchNorm output is exactly 0 (gamma = beta = 0) still has its d gamma and d beta
+__global__ void lc_bn_bwd_kernel(const float* dlogits, const float* W, const float* xhat, const float* stat, const float* gamma,
+                                 const float* drop, const int32_t* step_dev, unsigned long long seed, uint32_t thresh24, float inv_keep, int B,
+                                 int SQ, int D, int NC, float* dgamma, float* dbeta, float* dctx, float* d_hlast) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
+    const uint32_t step = step_dev ? (uint32_t)step_dev[0] : 0u;
     float s1 = 0.f, s2 = 0.f;
     for (int b = 0; b < B; ++b) {
         const long long o = (long long)b * D + d;
         float dy = 0.f;
         for (int c = 0; c < NC; ++c) dy += dlogits[(long long)b * NC + c] * W[(long long)c * D + d];
-        const float bn = bnout[o];
-        const float k = bn != 0.f ? y[o] / bn : 0.f;  // the keep mask value (0 or 1/(1-p)); bn == 0 contributes nothing anyway
-        const float dz = dy * k;
+        const float dz = dy * lc_keep(drop, step_dev != nullptr, seed, step, o, thresh24, inv_keep);
         dctx[o] = dz;
         s1 += dz;
         s2 += dz * xhat[o];
@@ -290,13 +303,15 @@ extern "C" int dpc_lc_head_bwd(const dpc_lc_head_desc* c, dpc_stream_t stream_) 
     hipStream_t stream = (hipStream_t)stream_;
     if (!c || c->B <= 0 || c->SQ <= 0 || c->D <= 0 || c->num_class <= 0) return DPC_ERR_ARG;
     if (!c->train) return DPC_ERR_ARG;  // eval-mode BatchNorm1d has no batch-statistics backward here (the reference never needs it)
-    if (!c->dlogits || !c->y || !c->bn_out || !c->xhat || !c->stat || !c->bn_weight || !c->fc_weight || !c->g_fc_weight || !c->g_fc_bias ||
+    if (!c->dlogits || !c->y || !c->xhat || !c->stat || !c->bn_weight || !c->fc_weight || !c->g_fc_weight || !c->g_fc_bias ||
         !c->g_bn_weight || !c->g_bn_bias || !c->dctx || !c->d_hlast)
         return DPC_ERR_ARG;
+    if (!(c->p_drop >= 0.f) || !(c->p_drop < 1.f)) return DPC_ERR_ARG;
     DPC_LAUNCH(lc_fc_wgrad_kernel, dim3(c->num_class), dim3(256), stream, (const float*)c->dlogits, (const float*)c->y, c->B, c->D, c->num_class,
                c->g_fc_weight, c->g_fc_bias);
-    DPC_LAUNCH(lc_bn_bwd_kernel, dim3((c->D + 255) / 256), dim3(256), stream, (const float*)c->dlogits, c->fc_weight, (const float*)c->y,
-               (const float*)c->bn_out, (const float*)c->xhat, (const float*)c->stat, c->bn_weight, c->B, c->SQ, c->D, c->num_class, c->g_bn_weight,
-               c->g_bn_bias, c->dctx, c->d_hlast);
+    const int32_t* step_dev = (!c->drop_mask && c->p_drop > 0.f) ? c->step_dev : nullptr;  // as dpc_lc_head_fwd resolved it
+    DPC_LAUNCH(lc_bn_bwd_kernel, dim3((c->D + 255) / 256), dim3(256), stream, (const float*)c->dlogits, c->fc_weight, (const float*)c->xhat,
+               (const float*)c->stat, c->bn_weight, c->drop_mask, step_dev, (unsigned long long)c->seed, dropout_thresh24(c->p_drop),
+               1.f / (1.f - c->p_drop), c->B, c->SQ, c->D, c->num_class, c->g_bn_weight, c->g_bn_bias, c->dctx, c->d_hlast);
     return dpc_launch_status();
 }

@@ -369,7 +369,9 @@ int dpc_gru_chain_bwd(const dpc_gru_chain_desc* c, dpc_stream_t stream);
  *  - relu_tpool: feat[n][(b,s)][d] = mean_t relu(x[b*N+n][t][s][d])  (ReLU BEFORE the temporal mean, model_3d_lc.py:52-54)
  *    and its backward dx = (x > 0) d_feat / T;
  *  - the head (model_3d_lc.py:58-64, eval/test.py:244-255): spatial mean of the last ConvGRU state -> BatchNorm1d ->
- *    Dropout(p) -> Linear -> CrossEntropyLoss + top-1, forward and backward.  result[0..1] = mean loss, accuracy. */
+ *    Dropout(p) -> Linear -> CrossEntropyLoss + top-1, forward and backward.  result[0..1] = mean loss, accuracy.
+ *    dpc_lc_head_bwd takes the Dropout keep values from where the forward took them (drop_mask, else the Philox draw of
+ *    (seed, step_dev[0]), else 1): call it with the descriptor of the train-mode forward, before step_dev advances. */
 int dpc_bn_finalize_running(const float* partials, int32_t rows, int32_t C, double count, const float* gamma, const float* beta,
                             float eps, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
                             float* running_var, int64_t* num_batches_tracked, float momentum, dpc_stream_t stream);

@@ -706,12 +706,13 @@ def philox4x32_10_np(ctr, key):
     return np.stack(c, 1).astype(np.uint32)
 
 
-def dropout_mask_np(n, p, seed, step):
+def dropout_mask_np(n, p, seed, step, stream=0):
     import numpy as np
     nb = (n + 3) // 4
     ctr = np.zeros((nb, 4), np.uint32)
     ctr[:, 0] = np.arange(nb, dtype=np.uint32)
     ctr[:, 1] = step
+    ctr[:, 2] = stream
     r = philox4x32_10_np(ctr, (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)).reshape(-1)[:n]
     thresh = int(p * 16777216.0 + 0.5)
     return ((r >> 8) >= thresh).astype(np.float32) / np.float32(1.0 - p)
@@ -1088,3 +1089,415 @@ def case_gemm_nt_bf16out(k: K, M, N, Kd, seed=3, expect="score_gemm2_kernel<KS,O
     want = (A.double() @ B.double().t())
     assert relerr(out, want) < 2.0 ** -8          # one rounding of an f32 accumulator
     assert torch.equal(out.cpu(), want.float().to(dtype)) or (out.cpu().float() - want.float()).abs().max().item() <= 2.0 ** -7 * want.abs().max().item()
+
+
+# ---------------------------------------------------------------- the LC classifier's own kernels (csrc/lc_head.hip, bn.hip)
+def _chain_lc_setup(k: K, dtype, B, SQ, D, n_agg, P, seed):
+    """_chain_setup in the form LCEngine uses (dpc_amd/lc.py): P = 0 means n_steps = n_agg and no predictor buffers at all --
+    built as the P = 1 setup (the same n_steps) with the predictor's pointers cleared"""
+    d, dev, w, b, x, d_pred = _chain_setup(k, dtype, B, SQ, D, max(P, 1), n_agg, seed)
+    if P == 0:
+        d.P = 0
+        d.P1_all = d.pred = d.d_pred = d.dP1 = d.dP2 = None
+    return d, dev, w, b, x, d_pred
+
+
+def case_gru_chain_lc(k: K, dtype, B, SQ, D, n_agg, P=0, h0=False, seed=41):
+    """dpc_gru_chain_fwd/_bwd as the LC classifier drives them (eval/model_3d_lc.py:56-60): aggregation only (P = 0, n_steps =
+    n_agg, every predictor buffer NULL), the backward seeded through d_hlast = d loss / d (last state); h0 = a non-zero H_all[0];
+    P > 0 with d_hlast as well (include/dpc_hip.h: optional for any P).  Expectation: the f64 cell of case_gru_chain with
+    loss = sum(H_all[n_steps] * d_hlast) (+ sum(pred * d_pred)); case_gru_chain's bounds."""
+    d, dev, w, b, x, d_pred = _chain_lc_setup(k, dtype, B, SQ, D, n_agg, P, seed)
+    ns, M = n_agg + max(P, 1) - 1, B * SQ
+    g = torch.Generator().manual_seed(seed + 1)
+    masks = (torch.rand(ns, M, D, generator=g) > 0.1).float() / 0.9
+    d_hlast = torch.randn(M, D, generator=g) * 0.1
+    h_init = q(torch.randn(M, D, generator=g) * 0.5, dtype) if h0 else torch.zeros(M, D)
+    dev["H_all"][0] = k.t(h_init, dtype)
+    mdev, ddev = k.t(masks), k.t(d_hlast)
+    d.drop_masks, d.d_hlast = mdev.data_ptr(), ddev.data_ptr()
+    k.call("dpc_gru_chain_fwd", C.byref(d))
+    k.call("dpc_gru_chain_bwd", C.byref(d))
+    k.sync()
+    W = {n: v.double().requires_grad_() for n, v in w.items()}
+    Bs = {n: v.double().requires_grad_() for n, v in b.items()}
+    xs = x.double().requires_grad_()
+    qd = (lambda t: t) if dtype == torch.float32 else (lambda t: t + (t.detach().to(dtype).double() - t.detach()))  # straight-through rounding
+
+    def cell(xi, h):
+        c = torch.cat([xi, h], 1)
+        u = torch.sigmoid(c @ W["update"].t() + Bs["update"])
+        r = torch.sigmoid(c @ W["reset"].t() + Bs["reset"])
+        o = torch.tanh(torch.cat([xi, qd(h * r)], 1) @ W["out"].t() + Bs["out"])
+        return h * (1 - u) + o * u
+
+    h = h_init.double()
+    step, preds, hs = 0, [], [h]
+    for t in range(n_agg):
+        h = qd(cell(xs[t], h) * masks[step].double())
+        hs.append(h)
+        step += 1
+    for i in range(P):
+        p1 = qd(torch.relu(h @ W["p0"].t() + Bs["p0"]))
+        p2 = p1 @ W["p2"].t() + Bs["p2"]
+        preds.append(qd(p2))
+        if i < P - 1:
+            h = qd(cell(qd(torch.relu(p2)), h) * masks[step].double())
+            hs.append(h)
+            step += 1
+    assert len(hs) == ns + 1
+    loss = (hs[-1] * d_hlast.double()).sum()
+    if P > 0:
+        pred = torch.stack(preds, 1).view(B, SQ, P, D).permute(0, 2, 1, 3)
+        loss = loss + (pred * d_pred.double()).sum()
+    loss.backward()
+    t_f, t_b = (2e-5, 2e-4) if dtype == torch.float32 else (3e-2, 6e-2)
+    assert relerr(dev["H_all"][1:], torch.stack(hs[1:]).detach()) < t_f
+    assert torch.equal(dev["H_all"][0].cpu(), h_init.to(dtype))   # h_0 is read, never written
+    if P > 0:
+        assert relerr(dev["pred"], pred.detach()) < t_f
+    assert relerr(dev["d_x"], xs.grad) < t_b
+    G = dev["G_all"].double().cpu().view(ns * M, 3 * D)
+    Xa = dev["X_all"].double().cpu().view(ns * M, D)
+    Ha = dev["H_all"][:ns].double().cpu().view(ns * M, D)
+    HRa = dev["HR_all"].double().cpu().view(ns * M, D)
+    gW = {"update": torch.cat([G[:, :D].t() @ Xa, G[:, :D].t() @ Ha], 1), "reset": torch.cat([G[:, D:2 * D].t() @ Xa, G[:, D:2 * D].t() @ Ha], 1),
+          "out": torch.cat([G[:, 2 * D:].t() @ Xa, G[:, 2 * D:].t() @ HRa], 1)}
+    gB = {"update": G[:, :D].sum(0), "reset": G[:, D:2 * D].sum(0), "out": G[:, 2 * D:].sum(0)}
+    if P > 0:
+        Hp = dev["H_all"][n_agg:].double().cpu().view(P * M, D)
+        gW["p0"] = dev["dP1"].double().cpu().view(P * M, D).t() @ Hp
+        gW["p2"] = dev["dP2"].double().cpu().view(P * M, D).t() @ dev["P1_all"].double().cpu().view(P * M, D)
+        gB["p0"], gB["p2"] = dev["dP1"].double().cpu().view(P * M, D).sum(0), dev["dP2"].double().cpu().view(P * M, D).sum(0)
+    for n in gW:
+        assert relerr(gW[n], W[n].grad) < t_b, n
+    for n in gB:
+        assert relerr(gB[n], Bs[n].grad) < t_b, n
+
+
+def case_gru_chain_lc_philox(k: K, dtype, B, SQ, D, n_agg, seed=42):
+    """the P = 0 recurrence with masks drawn in the kernel == the masks dpc_dropout_mask writes for the same (seed, step), injected
+    explicitly: bit-identical states and gradients; eval mode (neither masks nor a step counter) differs"""
+    M = B * SQ
+    step = torch.tensor([6], dtype=torch.int32, device=k.dev)
+    g = torch.Generator().manual_seed(seed + 1)
+    ddev = k.t(torch.randn(M, D, generator=g) * 0.1)
+    d1, dev1, *_ = _chain_lc_setup(k, dtype, B, SQ, D, n_agg, 0, seed)
+    d1.step_dev, d1.d_hlast = step.data_ptr(), ddev.data_ptr()
+    k.call("dpc_gru_chain_fwd", C.byref(d1))
+    k.call("dpc_gru_chain_bwd", C.byref(d1))
+    d2, dev2, *_ = _chain_lc_setup(k, dtype, B, SQ, D, n_agg, 0, seed)
+    masks = k.empty(n_agg, M, D)
+    k.call("dpc_dropout_mask", masks, masks.numel(), 0.1, 233, step)
+    d2.drop_masks, d2.d_hlast = masks.data_ptr(), ddev.data_ptr()
+    k.call("dpc_gru_chain_fwd", C.byref(d2))
+    k.call("dpc_gru_chain_bwd", C.byref(d2))
+    k.sync()
+    for f in ("H_all", "HR_all", "d_x", "G_all"):
+        assert torch.equal(dev1[f], dev2[f]), f
+    assert 0.85 < (masks > 0).float().mean().item() < 0.95
+    d3, dev3, *_ = _chain_lc_setup(k, dtype, B, SQ, D, n_agg, 0, seed)
+    k.call("dpc_gru_chain_fwd", C.byref(d3))
+    k.sync()
+    assert not torch.equal(dev3["H_all"], dev1["H_all"])
+
+
+LC_MOMENTUM, LC_EPS = 0.1, 1e-5
+LC_OFFSET_SPREAD = 0.02    # std of a clip's context around 0.9 in the `offset` variant (widened from 0.003, see case_lc_head)
+_LC_BUFS = ("ctx", "xhat", "bn_out", "y", "stat", "logits", "dlogits", "row_ws", "result", "g_fc_weight", "g_fc_bias", "g_bn_weight",
+            "g_bn_bias", "dctx", "d_hlast")
+
+
+def _lc_head_chain(inp, dt, explicit):
+    """the head as a chain of torch CPU ops in `dt`: spatial mean -> BatchNorm1d (train) -> keep mask -> Linear -> cross_entropy
+    (mean), autograd for the gradients, then the eval-mode forward from the updated running buffers.  explicit: BatchNorm written
+    out (the f64 expectation); else F.batch_norm (the f32 chain the reference model itself runs, eval/model_3d_lc.py:58-64)"""
+    B, SQ, D = inp["B"], inp["SQ"], inp["D"]
+    h = inp["h"].to(dt).requires_grad_()
+    gam, bet, W, bias = (inp[n].to(dt).requires_grad_() for n in ("gamma", "beta", "W", "bias"))
+    rm, rv, keep, tgt = inp["rm"].to(dt).clone(), inp["rv"].to(dt).clone(), inp["keep"].to(dt), inp["target"]
+    ctx = h.view(B, SQ, D).mean(1)
+    mean, var = ctx.mean(0), ctx.var(0, unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + LC_EPS)
+    if explicit:
+        xhat = (ctx - mean) * invstd
+        bn = xhat * gam + bet
+        unb = var * B / (B - 1) if B > 1 else var
+        rm = (1 - LC_MOMENTUM) * rm + LC_MOMENTUM * mean.detach()
+        rv = (1 - LC_MOMENTUM) * rv + LC_MOMENTUM * unb.detach()
+        bn_e = (ctx.detach() - rm) / torch.sqrt(rv + LC_EPS) * gam.detach() + bet.detach()
+    else:
+        xhat = F.batch_norm(ctx, None, None, None, None, True, LC_MOMENTUM, LC_EPS)
+        bn = F.batch_norm(ctx, rm, rv, gam, bet, True, LC_MOMENTUM, LC_EPS)   # updates rm / rv in place
+        bn_e = F.batch_norm(ctx.detach(), rm, rv, gam.detach(), bet.detach(), False, LC_MOMENTUM, LC_EPS)
+    y = bn * keep
+    logits = F.linear(y, W, bias)
+    logits.retain_grad()
+    loss = F.cross_entropy(logits, tgt)
+    loss.backward()
+    with torch.no_grad():
+        logits_e = F.linear(bn_e, W, bias)
+    out = dict(ctx=ctx, xhat=xhat, bn_out=bn, y=y, stat_mean=mean, stat_invstd=invstd, logits=logits, loss=loss.view(1), dlogits=logits.grad,
+               g_fc_weight=W.grad, g_fc_bias=bias.grad, g_bn_weight=gam.grad, g_bn_bias=bet.grad, d_hlast=h.grad, running_mean=rm,
+               running_var=rv, eval_bn_out=bn_e, eval_logits=logits_e)
+    return {n: v.detach().double() for n, v in out.items()}
+
+
+def _lc_head_inputs(dtype, B, SQ, D, NC, variant, seed):
+    g = torch.Generator().manual_seed(seed)
+    if variant == "offset":   # every clip's context = 0.9 +- LC_OFFSET_SPREAD per channel; the spatial part has zero mean
+        e = torch.randn(B, SQ, D, generator=g) * 1e-3
+        h = 0.9 + LC_OFFSET_SPREAD * torch.randn(B, 1, D, generator=g) + (e - e.mean(1, keepdim=True))
+    else:
+        h = torch.randn(B, SQ, D, generator=g) * 0.3
+    inp = dict(B=B, SQ=SQ, D=D, NC=NC, h=q(h.reshape(B * SQ, D), dtype), gamma=torch.rand(D, generator=g) + 0.5,
+               beta=torch.randn(D, generator=g) * 0.3, rm=torch.randn(D, generator=g) * 0.2, rv=torch.rand(D, generator=g) + 0.5,
+               W=torch.randn(NC, D, generator=g) / D ** 0.5, bias=torch.randn(NC, generator=g) * 0.1,
+               target=torch.randint(0, NC, (B,), generator=g), keep=(torch.rand(B, D, generator=g) > 0.5).float() / 0.5)
+    if variant == "dead_channel":
+        inp["gamma"][1] = 0.0
+        inp["beta"][1] = 0.0          # channel 1: BatchNorm output exactly 0 for every clip
+        inp["beta"][2] = 0.0          # channel 2: zero shift only
+        inp["keep"][0::2, 1], inp["keep"][1::2, 1] = 2.0, 0.0   # the dead channel keeps every other clip: its gradients are not 0
+    elif variant == "ties":
+        lo, hi = 3, 7
+        inp["W"][hi] = inp["W"][lo]
+        inp["bias"][lo] = inp["bias"][hi] = 12.0                 # the tied pair is the maximum of every row (asserted on the reference)
+        inp["target"] = torch.tensor([lo, hi, lo, 0, NC - 1])[torch.arange(B) % 5]   # more rows at the lower index than at the higher
+    elif variant == "hot":
+        lg = _lc_head_chain(inp, torch.float64, True)["logits"]
+        inp["W"] = inp["W"] * (80.0 / lg.abs().max().item())    # logits span about +-80
+    else:
+        assert variant in ("centred", "offset")
+    return inp
+
+
+def lc_head_reference(dtype, B, SQ, D, NC, variant, seed=51):
+    """inputs, f64 expectation, and the bound of every compared quantity: 8 x the error of the f32 torch chain against the f64
+    expectation (max-abs relative to the tensor's max-abs, as relerr), floor 1e-6 -- from the reference alone"""
+    inp = _lc_head_inputs(dtype, B, SQ, D, NC, variant, seed)
+    want = _lc_head_chain(inp, torch.float64, True)
+    f32 = _lc_head_chain(inp, torch.float32, False)
+    if variant == "dead_channel":   # the dead channel on its own, relative to ITS reference value: against the tensor's max-abs it can hide
+        for r in (want, f32):
+            r["g_bn_weight_dead"], r["g_bn_bias_dead"] = r["g_bn_weight"][1:2], r["g_bn_bias"][1:2]
+        assert want["g_bn_weight_dead"].abs().item() > 1e-3 and want["g_bn_bias_dead"].abs().item() > 1e-3
+    e32 = {n: relerr(f32[n], want[n]) for n in want}
+    bound = {n: max(8.0 * e, 1e-6) for n, e in e32.items()}
+    lg = want["logits"].clone()
+    if variant == "ties":
+        assert (lg[:, 3] - lg[:, 7]).abs().max().item() < 1e-12 and bool((lg[:, 3:4] > lg[:, [c for c in range(NC) if c not in (3, 7)]]).all())
+        lg[:, 7] = lg[:, 3]       # bit-exact in the expectation too, whatever the matmul's summation order
+    first_max = (lg == lg.max(1, keepdim=True).values).double().argmax(1)   # the first maximum wins (torch.max, eval/test.py:250)
+    hits = (first_max == inp["target"]).double()
+    if variant == "ties":   # rows target the lower and the higher index in different numbers: "last maximum wins" gives another accuracy
+        n_lo, n_hi = int((inp["target"] == 3).sum()), int((inp["target"] == 7).sum())
+        assert n_lo > n_hi > 0 and hits.sum().item() == n_lo
+    return inp, want, e32, bound, hits
+
+
+def _lc_head_desc(k: K, dtype, inp, p_drop, keep=None, step=None, seed=667, nbt0=7):
+    B, SQ, D, NC = inp["B"], inp["SQ"], inp["D"], inp["NC"]
+    t = {n: k.zeros(*s) for n, s in (("ctx", (B, D)), ("xhat", (B, D)), ("bn_out", (B, D)), ("y", (B, D)), ("dctx", (B, D)), ("stat", (2, D)),
+                                    ("logits", (B, NC)), ("dlogits", (B, NC)), ("row_ws", (B, 2)), ("result", (2,)), ("g_fc_weight", (NC, D)),
+                                    ("g_fc_bias", (NC,)), ("g_bn_weight", (D,)), ("g_bn_bias", (D,)), ("d_hlast", (B * SQ, D)))}
+    t.update(h_last=k.t(inp["h"], dtype), bn_weight=k.t(inp["gamma"]), bn_bias=k.t(inp["beta"]), bn_running_mean=k.t(inp["rm"].clone()),
+             bn_running_var=k.t(inp["rv"].clone()), bn_num_batches=torch.full((), nbt0, dtype=torch.int64, device=k.dev),
+             fc_weight=k.t(inp["W"]), fc_bias=k.t(inp["bias"]), target=k.t(inp["target"]))
+    d = L.LcHeadDesc()
+    d.dtype, d.B, d.SQ, d.D, d.num_class, d.train = L.dtype_code(dtype), B, SQ, D, NC, 1
+    d.p_drop, d.momentum, d.eps, d.seed = p_drop, LC_MOMENTUM, LC_EPS, seed
+    if keep is not None:
+        t["drop_mask"] = k.t(keep)
+    if step is not None:
+        t["step_dev"] = step
+    for n, v in t.items():
+        setattr(d, n, v.data_ptr())
+    return d, t
+
+
+def case_lc_head(k: K, dtype, B, SQ, D, NC, variant):
+    """dpc_lc_head_fwd (train) -> dpc_lc_head_bwd -> dpc_lc_head_fwd (eval) against f64 autograd over spatial mean -> BatchNorm1d ->
+    keep mask -> Linear -> cross_entropy (lc_head_reference).  h_last is quantised to `dtype` first; everything after it is f32 in
+    the kernel, so both dtypes get the same bound: per quantity 8 x the error of the f32 torch chain (F.batch_norm, F.linear,
+    F.cross_entropy, autograd) on the same inputs against the f64 expectation, floor 1e-6; the case asserts that no bound exceeds
+    tol(f32).  The margin of 8 covers another summation order over up to 300 channels / 1024 classes.
+
+    Worst f32-torch error over the compared quantities, measured on the CPU, f32 [bf16] input (worst quantity of the f32 run):
+      at (16, 16, 256, 101): centred 6.0e-7 [6.4e-7] (eval_logits), offset 5.2e-6 [1.6e-6] (y), dead_channel 6.4e-7 [5.7e-7] (d_hlast),
+        ties 3.6e-7 [4.9e-7] (g_bn_weight), hot 1.9e-6 [1.8e-6] (dlogits);
+      at (6, 3, 40, 11): centred 1.9e-7 [2.4e-7], offset 6.2e-6 [6.1e-6] (xhat), dead_channel 2.1e-7 [5.1e-7], ties 1.6e-7 [1.3e-7],
+        hot 2.7e-7 [5.6e-7].
+    `offset`: every clip's context is 0.9 +- LC_OFFSET_SPREAD per channel.  At a spread of 0.003 torch's own f32 BatchNorm chain is
+    NOT within 1e-5 (3.1e-5 at (16, 16, 256, 101), g_bn_weight; 1.6e-5 at (6, 3, 40, 11), xhat: ctx is an f32 mean of values near
+    0.9, half an ulp of it is 3e-8 = 1e-5 of the spread), which would put 8 x that above tol(f32).  The spread is therefore widened:
+    of 0.005 / 0.008 / 0.01 / 0.015 / 0.02, 0.015 is the first within 1e-5 at both shapes and both dtypes (<= 7.6e-6); 0.02
+    (<= 6.2e-6) is used, for headroom on a CPU whose torch sums in another order (the case asserts 8 x the error <= tol(f32)).
+    |mean| / std is still 45: s2/B - mean^2 in f32 misses invstd by 1.5e-3 at (6, 3, 40, 11), where the bound is 8e-6."""
+    inp, want, e32, bound, hits = lc_head_reference(dtype, B, SQ, D, NC, variant)
+    worst = max(bound.values())
+    assert worst <= tol(torch.float32), (worst, max(e32, key=e32.get))
+    d, t = _lc_head_desc(k, dtype, inp, 0.5, keep=inp["keep"])
+    k.call("dpc_lc_head_fwd", C.byref(d))
+    k.call("dpc_lc_head_bwd", C.byref(d))
+    k.sync()
+    got = {n: t[n].detach().cpu().clone() for n in _LC_BUFS}
+    got.update(stat_mean=got["stat"][0], stat_invstd=got["stat"][1], loss=got["result"][:1], running_mean=t["bn_running_mean"].cpu().clone(),
+               running_var=t["bn_running_var"].cpu().clone())
+    assert int(t["bn_num_batches"]) == 8
+    d.train = 0
+    k.call("dpc_lc_head_fwd", C.byref(d))
+    k.sync()
+    got.update(eval_bn_out=t["bn_out"].cpu(), eval_logits=t["logits"].cpu())
+    assert int(t["bn_num_batches"]) == 8                                       # unchanged by eval, as are the running buffers
+    assert torch.equal(t["bn_running_mean"].cpu(), got["running_mean"]) and torch.equal(t["bn_running_var"].cpu(), got["running_var"])
+    if variant == "dead_channel":
+        got["g_bn_weight_dead"], got["g_bn_bias_dead"] = got["g_bn_weight"][1:2], got["g_bn_bias"][1:2]
+        assert got["bn_out"][:, 1].abs().max().item() == 0
+    errs = {n: relerr(got[n], want[n]) for n in want}
+    bad = {n: (errs[n], bound[n]) for n in want if not errs[n] < bound[n]}
+    assert not bad, f"(error, bound) {bad}"
+    assert torch.isfinite(got["loss"]).all() and torch.isfinite(got["dlogits"]).all()
+    assert torch.equal(got["row_ws"][:, 1].double(), hits)                      # the top-1 hit of every clip: the first maximum wins
+    assert got["result"][1].item() == pytest_approx(hits.mean().item())
+    if variant == "ties":
+        assert torch.equal(got["logits"][:, 3], got["logits"][:, 7])            # the tie is bit-exact in the kernel
+    return errs, e32
+
+
+def case_lc_head_rejects(k: K):
+    """the class scratch holds 1024 logits: num_class = 1025 is an argument error, not a launch"""
+    import pytest
+    inp = _lc_head_inputs(torch.float32, 2, 1, 8, 1025, "centred", 5)
+    d, t = _lc_head_desc(k, torch.float32, inp, 0.5, keep=inp["keep"])
+    with pytest.raises(L.DpcError, match=f"code {L.ERR_ARG}$"):
+        k.call("dpc_lc_head_fwd", C.byref(d))
+
+
+def case_lc_head_philox(k: K, B, SQ, D, NC, p, seed=667):
+    """drop_mask = NULL, step_dev set: the head draws its keep mask from Philox stream 1 of (seed, step) -- the bits
+    dropout_mask_np(B*D, p, seed, step, stream=1) gives, not those of the recurrence's stream 0; forward and backward equal the
+    run with that mask injected explicitly bit for bit; another step draws another mask"""
+    import numpy as np
+    f32 = torch.float32
+    inp = _lc_head_inputs(f32, B, SQ, D, NC, "centred", 52)
+    step = torch.tensor([4], dtype=torch.int32, device=k.dev)
+    d1, t1 = _lc_head_desc(k, f32, inp, p, step=step, seed=seed)
+    k.call("dpc_lc_head_fwd", C.byref(d1))
+    k.call("dpc_lc_head_bwd", C.byref(d1))
+    k.sync()
+    m1 = dropout_mask_np(B * D, p, seed, 4, stream=1).reshape(B, D)
+    m0 = dropout_mask_np(B * D, p, seed, 4, stream=0).reshape(B, D)
+    assert not np.array_equal(m1, m0)
+    y, bn = t1["y"].cpu(), t1["bn_out"].cpu()
+    nz = (bn != 0).numpy()
+    assert nz.mean() > 0.99
+    assert np.array_equal((y.numpy() != 0)[nz], (m1 != 0)[nz]) and not np.array_equal((y.numpy() != 0)[nz], (m0 != 0)[nz])
+    assert torch.equal(y, bn * torch.from_numpy(m1))                             # the keep VALUE too: one f32 product
+    assert abs(float((m1 != 0).mean()) - (1 - p)) < 4 * (p * (1 - p) / (B * D)) ** 0.5 + 1e-9
+    d2, t2 = _lc_head_desc(k, f32, inp, p, keep=torch.from_numpy(m1), seed=seed)
+    k.call("dpc_lc_head_fwd", C.byref(d2))
+    k.call("dpc_lc_head_bwd", C.byref(d2))
+    k.sync()
+    for n in _LC_BUFS + ("bn_running_mean", "bn_running_var", "bn_num_batches"):
+        assert torch.equal(t1[n], t2[n]), n
+    assert t1["g_bn_weight"].abs().max().item() > 0 and t1["d_hlast"].abs().max().item() > 0
+    step.fill_(5)
+    k.call("dpc_lc_head_fwd", C.byref(d1))
+    k.sync()
+    m5 = dropout_mask_np(B * D, p, seed, 5, stream=1).reshape(B, D)
+    assert not np.array_equal(m5, m1)
+    assert torch.equal(t1["y"].cpu(), t1["bn_out"].cpu() * torch.from_numpy(m5))
+
+
+def case_relu_tpool(k: K, dtype, B, N, T, SQ, D, seed=61):
+    """dpc_relu_tpool_fwd / _bwd (ReLU BEFORE the temporal mean, eval/model_3d_lc.py:52-54) against f64 relu(x).mean(1) and its
+    autograd, output layout [N][B*SQ][D], d_feat f32.  Planted in x: exact +0.0 and -0.0, negatives, and for bf16 subnormals of both
+    signs; dx must be exactly 0 wherever x <= 0 (torch's ReLU gradient at 0 is 0) and within tol(dtype) elsewhere."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B * N, T, SQ, D, generator=g)
+    flat = x.view(-1)
+    n = flat.numel()
+    flat[0::7] = 0.0
+    flat[3::11] = -0.0
+    flat[5::13] = -flat[5::13].abs() - 0.25
+    if dtype == torch.bfloat16:
+        flat[1::17] = 2.0 ** -130     # bf16 subnormals (the smallest normal is 2^-126): positive ones pass the ReLU
+        flat[2::19] = -(2.0 ** -130)
+    flat[n - 1] = 0.0                  # the last element of the last unit
+    x = q(x, dtype)
+    xd = x.double().requires_grad_()
+    feat = torch.relu(xd).view(B, N, T, SQ, D).mean(2).permute(1, 0, 2, 3).reshape(N, B * SQ, D)
+    d_feat = torch.randn(N, B * SQ, D, generator=g)
+    gx = torch.autograd.grad(feat, xd, d_feat.double())[0]
+    xk = k.t(x, dtype)
+    fk = k.empty(N, B * SQ, D, dtype=dtype)
+    k.call("dpc_relu_tpool_fwd", xk, L.dtype_code(dtype), B, N, T, SQ, D, fk)
+    dx = k.empty(B * N, T, SQ, D, dtype=dtype)
+    k.call("dpc_relu_tpool_bwd", xk, k.t(d_feat), L.dtype_code(dtype), B, N, T, SQ, D, dx)
+    k.sync()
+    assert relerr(fk, feat.detach()) < tol(dtype)
+    dxc = dx.float().cpu()
+    nonpos = x <= 0
+    assert nonpos.float().mean().item() > 0.5 and bool((x[nonpos] == 0).any())
+    assert bool((dxc[nonpos] == 0).all())
+    assert bool((gx[nonpos] == 0).all())                                        # the expectation agrees on the planted zeros
+    assert relerr(dxc, gx) < tol(dtype)
+    if dtype == torch.bfloat16:
+        sub = (x > 0) & (x < 2.0 ** -126)
+        assert bool(sub.any()) and bool((dxc[sub] != 0).all())                  # a positive subnormal is > 0
+
+
+def case_bn_finalize_running(k: K, rows, Cc, count=None, misalign=0, momentum=0.1, seed=11):
+    """dpc_bn_finalize_running on case_bn_finalize's table: mean / invstd / scale / shift bit-equal to dpc_bn_finalize's, the running
+    buffers (non-trivial start) against the f64 momentum update with the UNBIASED variance (count = 1: the biased one), rtol 1e-6
+    of the result (the momentum is the f32 value the C ABI passes), num_batches_tracked + 1 per launch whatever the grid, NULL
+    accepted; then dpc_bn_eval_coeffs from those buffers against f64, rtol 1e-6 of the result, shift included."""
+    g = torch.Generator().manual_seed(seed)
+    parts = torch.randn(rows, 2, Cc, generator=g)
+    parts[:, 1] = parts[:, 1].abs() * 3 + parts[:, 0] ** 2
+    count = float(rows * 7) if count is None else float(count)
+    gamma, beta = torch.rand(Cc, generator=g) + 0.5, torch.randn(Cc, generator=g)
+    rm0, rv0 = torch.randn(Cc, generator=g) * 0.5, torch.rand(Cc, generator=g) + 0.5
+    buf = k.zeros(rows * 2 * Cc + 4)
+    pk = buf[misalign:misalign + rows * 2 * Cc].view(rows, 2, Cc)
+    pk.copy_(parts)
+    s1, s2 = parts[:, 0].double().sum(0), parts[:, 1].double().sum(0)
+    m = s1 / count
+    var = (s2 / count - m * m).clamp_min(0)
+    unb = var * count / (count - 1.0) if count > 1.0 else var
+    base = [k.empty(Cc) for _ in range(4)]
+    k.call("dpc_bn_finalize", pk, rows, Cc, count, k.t(gamma), k.t(beta), 1e-5, *base)
+    out = [k.empty(Cc) for _ in range(4)]
+    rm, rv = k.t(rm0.clone()), k.t(rv0.clone())
+    nbt = torch.full((), 5, dtype=torch.int64, device=k.dev)
+    k.call("dpc_bn_finalize_running", pk, rows, Cc, count, k.t(gamma), k.t(beta), 1e-5, *out, rm, rv, nbt, momentum)
+    k.sync()
+    for a, b_, n in zip(out, base, ("mean", "invstd", "scale", "shift")):
+        assert torch.equal(a, b_), n
+    assert int(nbt) == 6
+    f = lambda t: t.cpu().double()  # noqa: E731
+    close = lambda got, exp: torch.allclose(f(got), exp, rtol=1e-6, atol=0)  # noqa: E731
+    mo = torch.tensor(momentum, dtype=torch.float32).double().item()
+    r1, r2 = (1 - mo) * rm0.double() + mo * m, (1 - mo) * rv0.double() + mo * unb
+    assert close(rm, r1), "running_mean"
+    assert close(rv, r2), "running_var"
+    if count > 1.0:   # teeth: the biased variance must not pass for the unbiased one
+        assert not close(rv, (1 - mo) * rv0.double() + mo * var)
+    rm1, rv1 = f(rm).clone(), f(rv).clone()   # the second update starts from the f32 values the first one stored
+    out2 = [k.empty(Cc) for _ in range(4)]
+    k.call("dpc_bn_finalize_running", pk, rows, Cc, count, k.t(gamma), k.t(beta), 1e-5, *out2, rm, rv, None, momentum)   # NULL counter
+    k.sync()
+    assert int(nbt) == 6 and all(torch.equal(a, b_) for a, b_ in zip(out2, base))
+    assert close(rm, (1 - mo) * rm1 + mo * m), "running_mean, second launch"
+    assert close(rv, (1 - mo) * rv1 + mo * unb), "running_var, second launch"
+    # eval: coefficients from the running buffers as they now stand on the device
+    rmd, rvd = f(rm), f(rv)
+    ev = [k.empty(Cc) for _ in range(4)]
+    k.call("dpc_bn_eval_coeffs", k.t(gamma), k.t(beta), rm, rv, 1e-5, Cc, *ev)
+    k.sync()
+    inv = 1.0 / torch.sqrt(rvd + 1e-5)
+    sc = gamma.double() * inv
+    assert torch.equal(ev[0], rm)
+    assert close(ev[1], inv) and close(ev[2], sc)
+    assert close(ev[3], beta.double() - rmd * sc), "shift"

@@ -289,6 +289,47 @@ def test_gru_chain_philox(k, dtype):
     kc.case_gru_chain_philox(k, dtype, 3, 16, 64, 2, 2)
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_gru_chain_lc(k, dtype):
+    """the recurrence as the LC classifier calls it: P = 0, backward seeded through d_hlast; 48 rows, a non-zero h_0, and the
+    P = 3 form with d_hlast on top of d_pred; in-kernel Philox masks == injected ones"""
+    kc.case_gru_chain_lc(k, dtype, 3, 16, 64, 3)
+    kc.case_gru_chain_lc(k, dtype, 2, 5, 32, 2, h0=True)
+    kc.case_gru_chain_lc(k, dtype, 2, 5, 32, 2, P=3)
+    kc.case_gru_chain_lc_philox(k, dtype, 3, 16, 64, 3)
+
+
+@pytest.mark.parametrize("waves", ["8", "4"])
+def test_gru_chain_lc_full_width(k, monkeypatch, waves):
+    """D = 256 with P = 0 under both wave counts: 36 rows, one full and one ragged row tile"""
+    monkeypatch.setenv("DPC_GRU_WAVES", waves)
+    kc.case_gru_chain_lc(k, BF16, 2, 18, 256, 2)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_lc_head(k, dtype):
+    for variant in ("centred", "offset", "dead_channel", "ties", "hot"):
+        kc.case_lc_head(k, dtype, 6, 3, 40, 11, variant)
+
+
+def test_lc_head_philox(k):
+    kc.case_lc_head_philox(k, 6, 2, 30, 11, 0.1)    # D no multiple of 4: the 4-element Philox blocks straddle rows
+    kc.case_lc_head_philox(k, 16, 4, 32, 11, 0.5)
+    kc.case_lc_head_rejects(k)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_relu_tpool(k, dtype):
+    kc.case_relu_tpool(k, dtype, 2, 3, 2, 4, 32)
+    kc.case_relu_tpool(k, dtype, 3, 2, 1, 9, 16)
+
+
+def test_bn_finalize_running(k):
+    kc.case_bn_finalize_running(k, 37, 70)
+    kc.case_bn_finalize_running(k, 129, 64, misalign=1)
+    kc.case_bn_finalize_running(k, 5, 64, count=1)
+
+
 def test_gru_chain_reference_fixture(k, golden_dir):
     import os
     import numpy as np

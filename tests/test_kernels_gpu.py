@@ -297,6 +297,69 @@ def test_gru_chain_four_waves(k, monkeypatch):
     kc.case_gru_chain_philox(k, F32, 3, 16, 256, 3, 5)
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("shape,kw", [
+    ((3, 16, 256, 8), {}),                # 48 rows: one full and one ragged 32-row tile
+    ((2, 49, 256, 8), {}),                # 224-pixel family: rows that straddle clips
+    ((5, 4, 32, 8), {}),                  # a single ragged tile; at D = 32 most waves own no column tile
+    ((16, 16, 256, 8), {"h0": True}),     # the fine-tuning batch, 8 workgroups, a non-zero h_0
+    ((3, 16, 256, 5), {"P": 3}),          # d_hlast on top of d_pred
+])
+def test_gru_chain_lc(k, dtype, shape, kw):
+    """the recurrence in the LC classifier's form (P = 0, n_steps = n_agg = 8, backward seeded through d_hlast)"""
+    kc.case_gru_chain_lc(k, dtype, *shape, **kw)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+def test_gru_chain_lc_philox(k, dtype):
+    kc.case_gru_chain_lc_philox(k, dtype, 3, 16, 256, 8)
+
+
+def test_gru_chain_lc_four_waves(k, monkeypatch):
+    monkeypatch.setenv("DPC_GRU_WAVES", "4")
+    kc.case_gru_chain_lc(k, BF16, 3, 16, 256, 8)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("shape,variant", [
+    ((16, 16, 256, 101), "centred"), ((16, 16, 256, 101), "offset"), ((16, 16, 256, 101), "dead_channel"), ((16, 16, 256, 101), "ties"),
+    ((16, 16, 256, 101), "hot"),
+    ((2, 4, 256, 101), "centred"),        # the smallest batch
+    ((5, 49, 256, 51), "centred"),
+    ((7, 3, 300, 1024), "centred"),       # two workgroups (the second ragged) in the per-channel kernels; four strided class passes
+    ((3, 1, 8, 2), "centred"),
+])
+def test_lc_head(k, dtype, shape, variant):
+    kc.case_lc_head(k, dtype, *shape, variant)
+
+
+def test_lc_head_philox(k):
+    kc.case_lc_head_philox(k, 16, 16, 256, 101, 0.5)
+    kc.case_lc_head_philox(k, 6, 2, 30, 11, 0.1)     # D no multiple of 4: the 4-element Philox blocks straddle rows
+
+
+def test_lc_head_rejects_too_many_classes(k):
+    kc.case_lc_head_rejects(k)
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("shape", [(4, 8, 2, 16, 256), (3, 8, 1, 49, 256), (2, 3, 5, 1, 8)])
+def test_relu_tpool(k, dtype, shape):
+    kc.case_relu_tpool(k, dtype, *shape)
+
+
+def test_relu_tpool_past_the_grid_cap(k):
+    """3 * 8 * 1367 * 256 / 4 = 2 099 712 units > 8192 workgroups x 256 threads: the grid-stride loop takes a second trip"""
+    kc.case_relu_tpool(k, F32, 3, 8, 1, 1367, 256)
+
+
+@pytest.mark.parametrize("rows,C,count,misalign", [(1, 64, None, 0), (3, 5, None, 0), (37, 70, None, 0), (131, 64, None, 0), (300, 128, None, 0),
+                                                   (1030, 64, None, 0), (256, 512, None, 0), (129, 64, None, 1), (5, 64, 1, 0)])
+def test_bn_finalize_running(k, rows, C, count, misalign):
+    """dpc_bn_finalize_running / dpc_bn_eval_coeffs on test_bn_finalize's tables; C = 512 launches 16 workgroups, one counter increment"""
+    kc.case_bn_finalize_running(k, rows, C, count, misalign)
+
+
 def test_gru_chain_reference_fixture(k, golden_dir):
     import os
     import numpy as np

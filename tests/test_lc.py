@@ -105,7 +105,7 @@ def test_engine_eval_and_train_vs_oracle(emu):
             assert torch.allclose(eng.BUF[k], v, rtol=1e-4, atol=1e-5), k
         else:
             assert int(eng.BUF[k]) == int(v) == 1, k
-    # ---- fused Adam on the LC arena (the Philox form of both dropouts is covered at kernel level: test_lc_head_philox)
+    # ---- fused Adam on the LC arena (the Philox form of both dropouts is covered at kernel level: kcases.case_gru_chain_lc_philox / case_lc_head_philox)
     before = eng.flat_p.clone()
     eng.adam_step()
     assert eng.step_count == 1 and not torch.equal(before, eng.flat_p)
