@@ -53,7 +53,16 @@ class LcHeadDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("step_dev", "drop_mask", "h_last", "bn_weight", "bn_bias", "bn_running_mean", "bn_running_var",
                                            "bn_num_batches", "fc_weight", "fc_bias", "target", "ctx", "xhat", "bn_out", "y", "stat",
                                            "logits", "dlogits", "row_ws", "result", "g_fc_weight", "g_fc_bias", "g_bn_weight",
-                                           "g_bn_bias", "dctx", "d_hlast")])
+                                           "g_bn_bias", "dctx", "d_hlast", "d_bn_out")])
+
+
+class AdamSegment(C.Structure):
+    """struct dpc_adam_segment (include/dpc_hip.h)"""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float), ("active", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+ADAM_MAX_SEGMENTS = 512   # DPC_ADAM_MAX_SEGMENTS
 
 
 class ConvEpilogue(C.Structure):
@@ -123,6 +132,7 @@ _SIGS = {
     "dpc_ce_topk_bf16": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp],
     "dpc_step_advance": [_vp, _vp, _f64, _f64, _vp],
     "dpc_adam_dev": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp],
+    "dpc_adam_groups_dev": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp],
     "dpc_counter_advance": [_vp, _vp],
     "dpc_copy2d_f32": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "dpc_copy2d_multi": [_vp, _i32, _i32, _vp],

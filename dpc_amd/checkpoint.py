@@ -71,19 +71,45 @@ def optimizer_state_dict(eng) -> dict:
     return {"state": state, "param_groups": [group]}
 
 
-def load_optimizer_state(eng, opt_sd: dict, use_saved_lr: bool = True) -> None:
-    """inverse of optimizer_state_dict; accepts what the reference's torch.optim.Adam wrote"""
-    names = list(eng.PRM.keys())
+def grouped_optimizer_state_dict(eng, groups, updated=None) -> dict:
+    """the fused-Adam state under parameter groups, as torch.optim.Adam.state_dict() lays it out: ``param_groups`` has one entry per
+    group ({'params': [parameter names], 'lr', 'weight_decay'} each), parameter ids count through the groups in order, and ``state``
+    holds only the parameters named in `updated` (default: every grouped parameter once a step has run) -- torch creates a
+    parameter's state at its first update, so a frozen one has none.  ``step`` is the engine's one counter for all of them."""
+    state, out_groups, i = {}, [], 0
+    for g in groups:
+        ks = list(g["params"])
+        for k in ks:
+            if eng.step_count > 0 and (updated is None or k in updated):
+                o, n = eng.offsets[k]
+                state[i] = {"step": torch.tensor(float(eng.step_count)),
+                            "exp_avg": eng.flat_m[o:o + n].detach().cpu().clone().view(eng.shapes[k]),
+                            "exp_avg_sq": eng.flat_v[o:o + n].detach().cpu().clone().view(eng.shapes[k])}
+            i += 1
+        og = _adam_group_defaults(float(g["lr"]), float(g.get("weight_decay", 0.0)))
+        if "initial_lr" in g:
+            og["initial_lr"] = g["initial_lr"]
+        og["params"] = list(range(i - len(ks), i))
+        out_groups.append(og)
+    return {"state": state, "param_groups": out_groups}
+
+
+def load_optimizer_state(eng, opt_sd: dict, use_saved_lr: bool = True, names=None) -> None:
+    """inverse of optimizer_state_dict / grouped_optimizer_state_dict; accepts what the reference's torch.optim.Adam wrote.
+    names: the parameter names the file's ids count through, group after group (default: every parameter in registration
+    order); the moments of every other parameter are zeroed"""
+    names = list(eng.PRM.keys()) if names is None else list(names)
     groups = opt_sd["param_groups"]
     ids = [i for g in groups for i in g["params"]]
     if len(ids) != len(names):
         raise ValueError(f"loaded state dict contains {len(ids)} parameters, the model has {len(names)} "
                          "(torch.optim.Optimizer.load_state_dict raises the same way)")
     g0 = groups[0]
-    if g0.get("amsgrad") or g0.get("maximize"):
-        raise ValueError("amsgrad / maximize checkpoints are not supported (the reference uses neither, dpc/main.py:80-81)")
-    if tuple(g0.get("betas", (0.9, 0.999))) != (0.9, 0.999) or float(g0.get("eps", 1e-8)) != 1e-8:
-        raise ValueError("non-default Adam betas / eps in the checkpoint (the reference uses the defaults)")
+    for g in groups:
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("amsgrad / maximize checkpoints are not supported (the reference uses neither, dpc/main.py:80-81)")
+        if tuple(g.get("betas", (0.9, 0.999))) != (0.9, 0.999) or float(g.get("eps", 1e-8)) != 1e-8:
+            raise ValueError("non-default Adam betas / eps in the checkpoint (the reference uses the defaults)")
     # validate everything BEFORE touching the arenas: a rejected file must leave the engine's Adam state as it was
     steps, todo = set(), []
     for pos, i in enumerate(ids):

@@ -272,7 +272,7 @@ __global__ void lc_fc_wgrad_kernel(const float* dlogits, const float* y, int B, 
 // is, and a channel whose BatchNorm output is exactly 0 (gamma = beta = 0) still has its d gamma and d beta
 __global__ void lc_bn_bwd_kernel(const float* dlogits, const float* W, const float* xhat, const float* stat, const float* gamma,
                                  const float* drop, const int32_t* step_dev, unsigned long long seed, uint32_t thresh24, float inv_keep, int B,
-                                 int SQ, int D, int NC, float* dgamma, float* dbeta, float* dctx, float* d_hlast) {
+                                 int SQ, int D, int NC, float* dgamma, float* dbeta, float* dctx, float* d_hlast, const float* d_bn_out) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= D) return;
     const uint32_t step = step_dev ? (uint32_t)step_dev[0] : 0u;
@@ -281,7 +281,8 @@ __global__ void lc_bn_bwd_kernel(const float* dlogits, const float* W, const flo
         const long long o = (long long)b * D + d;
         float dy = 0.f;
         for (int c = 0; c < NC; ++c) dy += dlogits[(long long)b * NC + c] * W[(long long)c * D + d];
-        const float dz = dy * lc_keep(drop, step_dev != nullptr, seed, step, o, thresh24, inv_keep);
+        float dz = dy * lc_keep(drop, step_dev != nullptr, seed, step, o, thresh24, inv_keep);
+        if (d_bn_out) dz += d_bn_out[o];   // upstream gradient at `context` (the BatchNorm output before Dropout)
         dctx[o] = dz;
         s1 += dz;
         s2 += dz * xhat[o];
@@ -312,6 +313,6 @@ extern "C" int dpc_lc_head_bwd(const dpc_lc_head_desc* c, dpc_stream_t stream_) 
     const int32_t* step_dev = (!c->drop_mask && c->p_drop > 0.f) ? c->step_dev : nullptr;  // as dpc_lc_head_fwd resolved it
     DPC_LAUNCH(lc_bn_bwd_kernel, dim3((c->D + 255) / 256), dim3(256), stream, (const float*)c->dlogits, c->fc_weight, (const float*)c->xhat,
                (const float*)c->stat, c->bn_weight, c->drop_mask, step_dev, (unsigned long long)c->seed, dropout_thresh24(c->p_drop),
-               1.f / (1.f - c->p_drop), c->B, c->SQ, c->D, c->num_class, c->g_bn_weight, c->g_bn_bias, c->dctx, c->d_hlast);
+               1.f / (1.f - c->p_drop), c->B, c->SQ, c->D, c->num_class, c->g_bn_weight, c->g_bn_bias, c->dctx, c->d_hlast, c->d_bn_out);
     return dpc_launch_status();
 }

@@ -436,3 +436,71 @@ extern "C" int dpc_adam(float* p, const float* g, float* m, float* v, int64_t n,
     DPC_LAUNCH(adam_kernel, dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, beta1, beta2, eps, wd, bias_corr1, bias_corr2, grad_scale);
     return dpc_launch_status();
 }
+
+// ---- Adam over the flat arenas with per-segment learning rate / weight decay and frozen segments (parameter groups of
+// torch.optim.Adam: eval/test.py:76-84 builds one group per parameter; requires_grad = False or a group that leaves a parameter
+// out freezes it).  One launch.  The segment table (sorted, non-overlapping, begin / end multiples of 4 floats so that a 16-byte
+// unit never straddles two parameters; gaps = arena padding, never touched) is copied into LDS once per workgroup.  A workgroup
+// walks contiguous tiles of ADAM_TILE4 16-byte units: one binary search per tile for the first segment that ends behind the
+// tile's start, then every thread advances linearly from there (its units ascend).  A unit outside every segment or inside an
+// inactive one costs no load and no store.  Per-element arithmetic: adam_dev_kernel's.
+constexpr int ADAM_TILE4 = 1024;  // 16-byte units per tile: 4 per thread, 16 KB of each arena
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float* g, float* m, float* v, long long n4, long long ntiles,
+                                                          const dpc_adam_segment* segs, int nseg, float b1, float b2, float omb1,
+                                                          float omb2, float eps, const float* bc, float gscale) {
+    __shared__ long long s_begin[DPC_ADAM_MAX_SEGMENTS], s_end[DPC_ADAM_MAX_SEGMENTS];
+    __shared__ float s_lr[DPC_ADAM_MAX_SEGMENTS], s_wd[DPC_ADAM_MAX_SEGMENTS];   // lr < 0 marks an inactive segment
+    const int tid = threadIdx.x;
+    for (int s = tid; s < nseg; s += 256) {
+        s_begin[s] = segs[s].begin;
+        s_end[s] = segs[s].end;
+        s_lr[s] = segs[s].active ? segs[s].lr : -1.f;
+        s_wd[s] = segs[s].weight_decay;
+    }
+    __syncthreads();
+    const float bc1 = bc[0];
+    const float isb2 = 1.f / sqrtf(bc[1]);
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long t0 = tile * ADAM_TILE4 * 4;   // first float of the tile
+        int lo = 0, hi = nseg;                       // first segment with end > t0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_end[mid] <= t0) lo = mid + 1; else hi = mid;
+        }
+        int s = lo;
+        DPC_UNROLL
+        for (int j = 0; j < ADAM_TILE4 / 256; ++j) {
+            const long long i = tile * ADAM_TILE4 + tid + 256 * j;
+            const long long base = i * 4;
+            if (i >= n4) break;
+            while (s < nseg && s_end[s] <= base) ++s;
+            if (s >= nseg) break;
+            if (s_begin[s] > base || s_lr[s] < 0.f) continue;   // padding between segments, or frozen
+            const float step = s_lr[s] / bc1, wd = s_wd[s];
+            f32x4 pv = ((f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+            DPC_UNROLL
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * gscale + wd * pv[e];
+                mv[e] = b1 * mv[e] + omb1 * gg;
+                vv[e] = b2 * vv[e] + omb2 * gg * gg;
+                pv[e] -= step * mv[e] / (sqrtf(vv[e]) * isb2 + eps);
+            }
+            ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+        }
+    }
+}
+
+// n: floats in each arena, a multiple of 4 (the arenas keep every tensor 16-byte aligned).  The table is validated where it is built
+// (dpc_amd/engine.py: sorted, aligned, inside the arena); here only pointers and counts are.
+extern "C" int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                                   int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
+                                   float grad_scale, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!p || !g || !m || !v || n <= 0 || n % 4 || !segments_dev || n_segments <= 0 || n_segments > DPC_ADAM_MAX_SEGMENTS || !bias_corr_dev)
+        return DPC_ERR_ARG;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16) return DPC_ERR_ARG;
+    const long long n4 = n / 4, ntiles = (n4 + ADAM_TILE4 - 1) / ADAM_TILE4;
+    const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
+    DPC_LAUNCH(adam_groups_kernel, dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale);
+    return dpc_launch_status();
+}

@@ -535,6 +535,9 @@ class BackboneEngine:
         self._part_need = 0
         self._scratch: Dict[Tuple[int, ...], List[torch.Tensor]] = {}
         self._step_count = 0
+        self._groups, self._groups_key, self._seg_host, self._seg_dev, self._seg_n = None, None, None, None, 0   # parameter groups of the fused Adam (set_param_groups)
+        self.seg_uploads = 0          # host-to-device copies of the segment table so far
+        self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
         self.timer: Optional["KernelTimer"] = None
         self._tag: Optional[str] = None
@@ -893,6 +896,8 @@ class BackboneEngine:
         self.dev_draw.copy_(old.dev_draw)
         self._step_count = old._step_count
         self.lr, self.wd = old.lr, old.wd
+        if old.param_groups:
+            self.set_param_groups(old.param_groups)
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1024,18 +1029,109 @@ class BackboneEngine:
         self.dev_step.fill_(int(t))
         self.dev_draw.fill_(int(t))  # one draw per step in the engine-owned loop: a resumed run continues the same mask stream
 
+    def set_param_groups(self, groups=None):
+        """Parameter groups of the fused Adam (torch.optim.Adam over several groups: eval/test.py:76-84 gives every parameter its own).
+        groups: an iterable of dicts {'params': [parameter names], 'lr': float, 'weight_decay': float, 'frozen': bool (default False)};
+        a parameter named by no group is frozen, as is every parameter of a 'frozen' group: the update neither reads nor writes its
+        slices of the four arenas (torch skips a parameter without a gradient the same way).  None / () returns to the one-group
+        update (``self.lr`` / ``self.wd`` over the whole arena, dpc_adam_dev).
+
+        The segment table (csrc/loss.hip: dpc_adam_groups_dev) is built from ``self.offsets``, adjacent parameters with equal
+        values merged into one segment, and uploaded here -- only when a host value differs from what the device holds, so an lr
+        schedule that calls this once per epoch costs one small copy per change and a caller that passes the same values every
+        step costs none.  Never call it while a graph is being captured (the upload is a host-to-device copy).  The table lives in
+        one device buffer whose address never changes; a captured step (DPCEngine.capture_train_step) counts the table among the
+        values baked into it, so a replay after the groups changed raises instead of stepping with another table.
+
+        ONE step counter serves all groups: a parameter that is frozen for the first k steps and trained afterwards is updated
+        with the shared bias corrections 1 - beta^t of the run, where torch, which counts steps per parameter, would restart it at
+        t = 1.  (Its moments do start from zero either way.)"""
+        if not groups:
+            self._groups, self._groups_key, self._seg_host, self._seg_n = None, None, None, 0   # (the device buffer stays: a captured step may hold its address)
+            return
+        key = tuple((tuple(g["params"]), float(g["lr"]), float(g.get("weight_decay", 0.0)), bool(g.get("frozen", False))) for g in groups)
+        if key == self._groups_key:   # the values of the last call (an optimizer that passes its groups at every step): nothing to rebuild
+            return
+        names = list(self.offsets)
+        per_param: Dict[str, Tuple[float, float, bool]] = {}
+        norm = []
+        for g in groups:
+            lr, wd, frozen = float(g["lr"]), float(g.get("weight_decay", 0.0)), bool(g.get("frozen", False))
+            if not (lr >= 0.0) or not (wd >= 0.0):   # (NaN fails both)
+                raise ValueError(f"set_param_groups: lr and weight_decay must be non-negative numbers, got lr={lr}, weight_decay={wd}")
+            ks = list(g["params"])
+            for k in ks:
+                if k not in self.offsets:
+                    raise KeyError(f"set_param_groups: {k} is not a parameter of this engine")
+                if k in per_param:
+                    raise ValueError(f"set_param_groups: {k} appears in more than one parameter group")
+                per_param[k] = (lr, wd, not frozen)
+            norm.append({"params": ks, "lr": lr, "weight_decay": wd, "frozen": frozen})
+        segs = []   # [begin, end, lr, wd, active] in arena order; a parameter's slice is rounded up to its 16-byte slot
+        for k in names:
+            o, n = self.offsets[k]
+            lr, wd, active = per_param.get(k, (0.0, 0.0, False))
+            if not active:
+                lr = wd = 0.0
+            e = o + (n + 3) // 4 * 4
+            if segs and segs[-1][1] == o and tuple(segs[-1][2:]) == (lr, wd, active):
+                segs[-1][1] = e
+            else:
+                segs.append([o, e, lr, wd, active])
+        prev = 0
+        for b, e, _, _, _ in segs:   # the table is validated where it is built: sorted, 16-byte aligned, inside the arena
+            if b % 4 or e % 4 or b < prev or e <= b or e > self.numel:
+                raise ValueError(f"set_param_groups: bad segment [{b}, {e}) in an arena of {self.numel} floats")
+            prev = e
+        if len(segs) > L.ADAM_MAX_SEGMENTS:
+            raise ValueError(f"set_param_groups: {len(segs)} segments, the kernel's table holds {L.ADAM_MAX_SEGMENTS}")
+        tab = (L.AdamSegment * len(segs))()
+        for i, (b, e, lr, wd, active) in enumerate(segs):
+            tab[i] = L.AdamSegment(b, e, lr, wd, int(active), 0)
+        host = bytes(tab)
+        self._groups, self._groups_key = norm, key
+        if host != self._seg_host:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise L.DpcError("set_param_groups: the segment table changed while a graph is being captured")
+            if self._seg_dev is None:   # ONE device buffer of the kernel's capacity for the engine's life: its address never changes
+                self._seg_dev = torch.zeros(L.ADAM_MAX_SEGMENTS * C.sizeof(L.AdamSegment), dtype=torch.uint8, device=self.device)
+            raw = torch.frombuffer(bytearray(host), dtype=torch.uint8)
+            self._seg_dev[:raw.numel()].copy_(raw)
+            self._seg_host, self._seg_n = host, len(segs)
+            self.seg_uploads += 1
+
+    @property
+    def param_groups(self):
+        """what set_param_groups was given last (normalised), or None: the one-group update"""
+        return self._groups
+
+    def frozen_params(self):
+        """names of the parameters the grouped update leaves alone (empty without groups)"""
+        if not self.param_groups:
+            return []
+        live = {k for g in self._groups if not g["frozen"] for k in g["params"]}
+        return [k for k in self.offsets if k not in live]
+
     def adam_step(self, grad_scale: float = 1.0):
         self._step_count += 1
         self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
+        if self._groups:
+            self.call("dpc_adam_groups_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self._seg_dev, self._seg_n,
+                      0.9, 0.999, 1e-8, self.dev_bc, grad_scale)
+            return
         self.call("dpc_adam_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
                   self.wd, self.dev_bc, grad_scale)
+
+    def _first_bucket(self) -> torch.Tensor:
+        """the gradients finished last (stem + layer1): the second bucket of the two-bucket exchange"""
+        return self.flat_g[:self.grad_split]
 
     def _backward_and_exchange(self, allreduce=None):
         """the head's backward(), then the gradient exchange: two buckets (``allreduce.start`` on the tail while layer1 + stem
         are still running, ``allreduce.finish`` on the rest) or one call on the whole arena"""
         if allreduce is not None and hasattr(allreduce, "start"):
             self.backward(on_tail_ready=allreduce.start)
-            allreduce.finish(self.flat_g[:self.grad_split])
+            allreduce.finish(self._first_bucket())
         else:
             self.backward()
             if allreduce is not None:
@@ -1267,7 +1363,9 @@ class DPCEngine(BackboneEngine):
     def _baked_scalars(self) -> tuple:
         """host scalars a captured step carries as kernel arguments (a replay keeps the values of its capture)"""
         gd = self.gru_desc
-        return (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
+        base = (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
+        # with parameter groups the captured update reads the segment table: its contents belong to what a replay must still find
+        return base + ((self._seg_n, self._seg_host),) if self._groups else base
 
     def check_graph_capture(self):
         """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""

@@ -12,6 +12,10 @@ Same 2d3d-ResNet and ConvGRU kernels as the DPC-RNN step; what differs from ``DP
 ``LCEngine`` is the static-schedule engine (forward / backward / fused Adam on flat arenas, like ``DPCEngine``);
 ``LC`` is the drop-in ``nn.Module`` with the reference's constructor, ``forward(block) -> (output, context)`` and
 state_dict keys (running buffers included), so ``--pretrain`` of a DPC checkpoint and ``--test`` files load by key.
+In train mode the module's outputs carry an autograd node (``_LCOutput``), so the training lines of eval/test.py:224-255 run
+unchanged over it, with ``dpc_amd.optim.Adam`` as the optimizer: one parameter group per parameter (``--train_what ft``,
+eval/test.py:76-84), a 10x smaller backbone lr, or a linear probe on a frozen extractor (``requires_grad_(False)``), where the
+backward stops in front of the frozen part.
 """
 from __future__ import annotations
 
@@ -76,6 +80,8 @@ class LCEngine(BackboneEngine):
         self._build_gru(n_agg=N, n_steps=N, P=0)
         M = self.M
         self.d_hlast = self.empty((M, D), f32)
+        self._ran_backbone_backward = True
+        self.d_context = self.empty((B, D), f32)   # an upstream d loss / d context (backward's d_context) is staged here
         self.BUF["final_bn.running_mean"] = torch.zeros(D, dtype=f32, device=self.device)
         self.BUF["final_bn.running_var"] = torch.ones(D, dtype=f32, device=self.device)
         self.BUF["final_bn.num_batches_tracked"] = torch.zeros((), dtype=torch.int64, device=self.device)
@@ -156,15 +162,59 @@ class LCEngine(BackboneEngine):
         self.call("dpc_lc_head_fwd", C.byref(hd))
         return self.logits.view(B, 1, self.num_class), self.context.view(B, 1, D)
 
-    def backward(self, on_tail_ready=None):
-        """gradients of the mean CE loss of the last train-mode forward w.r.t. every parameter"""
+    def grad_wanted(self, wanted=None) -> Tuple[bool, bool]:
+        """(backbone, agg): whether any ``backbone.*`` / ``agg.*`` parameter needs a gradient.  wanted: the names that do, when the
+        caller knows (the module boundary passes what autograd asks for, and nothing else counts there).  None = the engine-owned
+        step: a parameter needs none when the grouped Adam leaves it alone (set_param_groups: frozen, or in no group) or it is
+        listed in ``no_grad_params``.  The backward stops at these two cut points only."""
+        if wanted is None:
+            skip = set(self.frozen_params()) | set(self.no_grad_params)
+            wanted = [k for k in self.offsets if k not in skip]
+        backbone = any(k.startswith("backbone.") for k in wanted)
+        return backbone, backbone or any(k.startswith("agg.") for k in wanted)
+
+    def _first_bucket(self) -> torch.Tensor:
+        """nothing of stem + layer1 to exchange when the backward stopped in front of the backbone (their slices hold no gradient)"""
+        return self.flat_g[:self.grad_split] if self._ran_backbone_backward else self.flat_g[:0]
+
+    def backward(self, on_tail_ready=None, d_output: Optional[torch.Tensor] = None, d_context: Optional[torch.Tensor] = None,
+                 wanted=None):
+        """Gradients of the last train-mode forward w.r.t. every parameter that needs one.  Without arguments: of the mean CE loss
+        (the forward's CE kernel left d loss / d logits in ``dlogits``).  Upstream form (torch autograd through LC.forward):
+        d_output [B,1,num_class] = d loss / d output replaces the CE gradient, d_context [B,1,D] = d loss / d context enters at the
+        BatchNorm1d output, ahead of the Dropout (``context`` is returned before it, model_3d_lc.py:60-64); either may be None (zero).
+
+        Truncation: when no ``backbone.*`` parameter needs a gradient (grad_wanted(wanted); wanted = the parameter names autograd asks
+        for at the module boundary, None = decided by the optimizer groups) the ReLU / temporal-mean backward and the
+        backbone's backward are not launched; when no ``agg.*`` parameter does either, neither are the ConvGRU's.  The gradient
+        slices of those parameters keep whatever they held.  The BatchNorm layers of such a frozen backbone still ran on batch
+        statistics and updated their running buffers in the forward -- requires_grad = False in torch, not .eval()."""
         if not self.train_mode:
             raise L.DpcError("LCEngine.backward needs a train-mode forward (BatchNorm with batch statistics)")
         B, N, SQ, D = self.B, self.N, self.SQ, self.D
         dc = L.dtype_code(self.cdtype)
-        self.call("dpc_lc_head_bwd", C.byref(self.head_desc))
-        self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
-        self._gru_param_grads(dc)
+        hd = self.head_desc
+        if d_output is not None or d_context is not None:
+            if d_output is None:
+                self.dlogits.zero_()
+            else:
+                self.dlogits.copy_(d_output.reshape(B, self.num_class))
+            if d_context is not None:
+                self.d_context.copy_(d_context.reshape(B, D))
+        hd.d_bn_out = self.d_context.data_ptr() if d_context is not None else None
+        self.call("dpc_lc_head_bwd", C.byref(hd))
+        hd.d_bn_out = None
+        need_backbone, need_agg = self.grad_wanted(wanted)
+        self._ran_backbone_backward = need_backbone
+        if need_agg:
+            self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
+            self._gru_param_grads(dc)
+        if not need_backbone:
+            if on_tail_ready is not None:   # the two-bucket exchange still gets its tail (the head's gradients live there; the
+                # frozen layers' slices in it travel along: one bucket, one collective); the first bucket is skipped (_first_bucket)
+                self.side_join()
+                on_tail_ready(self.flat_g[self.grad_split:])
+            return
         self.call("dpc_relu_tpool_bwd", self.blocks[-1].out, self.d_featrelu, dc, B, N, self.feat_shape[1], SQ, D, self.d_feat)
         self._backbone_backward(self.d_feat, on_tail_ready)
 
@@ -219,17 +269,76 @@ class LCEngine(BackboneEngine):
                   self.test_totals, self.test_confusion)
 
 
+class _LCOutput(torch.autograd.Function):
+    """(output, context) of a train-mode LC.forward with an autograd node, built like model._DPCScore: the backward runs the engine's
+    hand-written backward from the upstream gradients and hands autograd fresh views of the gradient arena"""
+
+    @staticmethod
+    def forward(ctx, model, block, target, masks, *params):
+        eng = model._engine
+        model._fwd_generation += 1   # the engine keeps ONE set of saved activations: the node is valid until the next forward, for one backward
+        gru_masks, fc_mask = masks if masks is not None else (None, None)
+        out, context = eng.forward(block, target, train=True, gru_masks=gru_masks, fc_mask=fc_mask)
+        ctx.model, ctx.generation, ctx.used = model, model._fwd_generation, False
+        ctx.set_materialize_grads(False)   # an output the loss does not use arrives as None, not as a zero tensor
+        return out.clone(), context.clone()
+
+    @staticmethod
+    def backward(ctx, d_output, d_context):
+        model = ctx.model
+        eng = model._engine
+        if ctx.generation != model._fwd_generation:
+            raise RuntimeError("dpc_amd.LC: backward of an output whose saved activations were overwritten by a later forward (the "
+                               "engine holds one step's activations; call backward before the next forward)")
+        if ctx.used:
+            raise RuntimeError("dpc_amd.LC: trying to backward through the graph a second time (activations are consumed in place "
+                               "by the backward kernels)")
+        ctx.used = True
+        names = model._param_names
+        params = model._params()
+        # what autograd asks for decides where the backward stops -- never the optimizer's groups: a parameter that requires a
+        # gradient gets a real one whether or not the last optimizer step left it out
+        wanted = [ctx.needs_input_grad[4 + i] for i in range(len(names))]
+        aliased = any(q.grad is not None and q.grad.data_ptr() == eng.G[k].data_ptr() for k, q in zip(names, params))
+        old = eng.flat_g.clone() if aliased else None   # .grad still set (no zero_grad): torch accumulates; the kernels overwrite the arena
+        if d_output is None and d_context is None:
+            d_output = torch.zeros_like(eng.logits)
+        eng.backward(d_output=d_output, d_context=d_context, wanted=[k for k, w in zip(names, wanted) if w])
+        need_backbone, need_agg = eng.grad_wanted([k for k, w in zip(names, wanted) if w])
+        src = eng.flat_g
+        if old is not None:   # autograd gets a copy of the new gradients; the arena (= the live .grad tensors) gets its old values back
+            src = eng.flat_g.clone()
+            eng.flat_g.copy_(old)
+        grads = []
+        for k, w in zip(names, wanted):
+            o, n = eng.offsets[k]
+            ran = need_backbone if k.startswith("backbone.") else (need_agg if k.startswith("agg.") else True)
+            grads.append(src[o:o + n].view(eng.shapes[k]) if (w and ran) else None)   # requires_grad = False: None, as torch gives
+        return (None, None, None, None) + tuple(grads)
+
+
 class LC(_EngineModule):
     """drop-in for eval/model_3d_lc.py:12: ``LC(sample_size, num_seq, seq_len, network, dropout, num_class)``,
-    ``forward(block) -> (output [B,1,num_class], context [B,1,D])``.  Inference and the engine's own train step are the
-    supported uses (``engine.train_step(block, target)``); torch autograd through forward is not wired for this head."""
+    ``forward(block) -> (output [B,1,num_class], context [B,1,D])``.  In train mode both carry an autograd node, so the reference's
+    loop runs as written (eval/test.py:229-255): ``loss = criterion(output.view(B*N, D), target); optimizer.zero_grad();
+    loss.backward(); optimizer.step()`` -- ``loss.backward()`` runs the engine's backward kernels from whatever gradient arrives at
+    ``output`` and ``context``; afterwards every parameter's ``.grad`` is a view of the gradient arena (it accumulates if ``.grad``
+    was still set), and ``dpc_amd.optim.Adam`` (parameter groups, frozen parameters) is the fused arena update.  A parameter with
+    ``requires_grad = False`` gets ``None``; when no ``backbone.*`` (and no ``agg.*``) parameter requires a gradient the backward
+    stops in front of the backbone (the ConvGRU) -- decided by ``requires_grad`` alone, never by which parameters an optimizer holds -- BatchNorm layers of such a frozen extractor still use batch statistics and update
+    their running buffers in train mode, as in torch.  One backward per forward, before the next forward.  Eval mode builds no graph
+    (the reference validates under ``no_grad``).  ``engine.train_step(block, target)`` remains the engine-owned step."""
     _SAVED_AS = "eval/test.py:205-214"
 
     def __init__(self, sample_size, num_seq, seq_len, network="resnet18", dropout=0.5, num_class=101,
                  compute_dtype=torch.float32, widths=LAYER_WIDTH, seed: int = 0, _simulator: Optional[L.Lib] = None):
         super().__init__(sample_size, num_seq, seq_len, network, compute_dtype, widths, _simulator)
         self.num_class, self.dropout = num_class, dropout
+        self._forced_masks = None    # tests: (gru_masks [N,M,D], fc_mask [B,D]), pre-scaled keep values for both dropouts
+        self._fwd_generation = 0
+        self._param_list = None
         shapes = lc_param_shapes(network, num_class, widths)
+        self._param_names = list(shapes)
         init = _init_reference_style(shapes, torch.Generator().manual_seed(seed))
         for k in lc_state_dict_keys(network, num_class, widths):
             if k.startswith("agg.cell_list.0."):
@@ -241,6 +350,13 @@ class LC(_EngineModule):
                 v = torch.zeros(C_) if k.endswith("running_mean") else (torch.ones(C_) if k.endswith("running_var") else torch.zeros((), dtype=torch.int64))
                 _attach(self, k, v, buffer=True)
         self.agg.cell_list = nn.ModuleList([self.agg.ConvGRUCell_00])
+
+    def _params(self):
+        """the Parameters in the engine's order (the objects never change: _ensure_engine re-points their .data)"""
+        if self._param_list is None:
+            named = dict(self.named_parameters())
+            self._param_list = [named[k] for k in self._param_names]
+        return self._param_list
 
     def _make_engine(self, B, dev):
         return LCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, B, dev, self.compute_dtype,
@@ -267,5 +383,7 @@ class LC(_EngineModule):
         self._engine.packed_for_step = -1  # the parameters may have been changed through the module since the last forward
         if target is None:
             target = torch.zeros(block.shape[0], dtype=torch.int64)
-        out, ctx = self._engine.forward(block.float(), target, train=self.training)
-        return out.clone(), ctx.clone()
+        if not self.training:
+            out, ctx = self._engine.forward(block.float(), target, train=False)
+            return out.clone(), ctx.clone()
+        return _LCOutput.apply(self, block.float(), target, self._forced_masks, *self._params())

@@ -30,6 +30,12 @@ below restates the multiplier; the fused Adam takes ``eng.lr`` per step.
 ``--train_what ft``: the reference gives parameters whose NAME contains 'resnet' or 'rnn' a 10x smaller lr
 (eval/test.py:76-84) -- but LC's parameters are called ``backbone.*`` / ``agg.*`` / ``final_*`` (model_3d_lc.py:29-45), so the
 filter never matches and every parameter trains at ``--lr``.  This entry does what the reference effectively does: one lr.
+Two values of this build give what the flag was meant to do, both through the grouped fused Adam (engine.set_param_groups; the
+epoch schedule scales every group, checkpoints written in these modes resume in them):
+``--train_what ft_backbone``: ``backbone.*`` and ``agg.*`` train at ``--lr / 10``, ``final_bn`` / ``final_fc`` at ``--lr``;
+``--train_what head``: only ``final_bn.*`` and ``final_fc.*`` train -- a linear probe on a frozen extractor.  The backward stops in
+front of the ConvGRU; the extractor's BatchNorm layers keep using batch statistics and updating their running buffers in train()
+(requires_grad = False in torch, and the only sensible mode after ``--pretrain``: a DPC checkpoint has no running statistics).
 """
 from __future__ import annotations
 
@@ -62,7 +68,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--gpu', default='0,1', type=str)
     parser.add_argument('--print_freq', default=5, type=int)
     parser.add_argument('--reset_lr', action='store_true', help='Reset learning rate when resume training?')
-    parser.add_argument('--train_what', default='last', type=str, help='Train what parameters?')
+    parser.add_argument('--train_what', default='last', type=str, help='Train what parameters?  ft / last / all as the reference; '
+                        'ft_backbone: backbone.* and agg.* at lr / 10; head: only final_bn.* and final_fc.* (frozen extractor)')
     parser.add_argument('--prefix', default='tmp', type=str)
     parser.add_argument('--img_dim', default=128, type=int)
     # additions of this build
@@ -146,7 +153,25 @@ def _worker(rank: int, world: int, args, port: int):
     num_epoch, best_acc, iteration = 0, 0.0, 0
     base_lr = args.lr
     milestones = lr_milestones(args.dataset, args.img_dim)
-    eng.lr = base_lr * lr_multiplier(0, 0.1, milestones, 1)  # LambdaLR's constructor step
+    # --train_what ft_backbone / head (additions of this build): parameter groups of the fused Adam, [(names, lr before the schedule)]
+    groups = None
+    extractor = [k for k in eng.offsets if k.startswith(('backbone.', 'agg.'))]
+    if args.train_what == 'ft_backbone':   # what eval/test.py:76-84 was written to do: the extractor at lr / 10
+        groups = [(extractor, base_lr / 10), ([k for k in eng.offsets if k not in extractor], base_lr)]
+        log('=> finetune backbone with smaller lr  [backbone.* and agg.* at lr / 10]')
+    elif args.train_what == 'head':        # linear probe: only final_bn.* and final_fc.* train; the backward stops in front of the ConvGRU
+        groups = [([k for k in eng.offsets if k.startswith(('final_bn.', 'final_fc.'))], base_lr)]
+        log('=> train only final_bn / final_fc on a frozen backbone + ConvGRU (batch statistics, running buffers updated)')
+
+    def set_lr(mult, saved=None):
+        """the schedule scales every group; saved: the groups' lrs of a resumed checkpoint"""
+        eng.lr = base_lr * mult
+        if groups is not None:
+            lrs = saved if saved is not None else [lr * mult for _, lr in groups]
+            eng.set_param_groups([{'params': ks, 'lr': lr, 'weight_decay': args.wd} for (ks, _), lr in zip(groups, lrs)])
+            eng.lr = lrs[-1]   # the log line's lr: the head group's
+
+    set_lr(lr_multiplier(0, 0.1, milestones, 1))  # LambdaLR's constructor step
     for path, what in ((args.test, 'test'), (args.resume, 'resume'), (args.pretrain, 'pretrain')):
         if not path or path == 'random' or (what == 'pretrain' and args.resume):
             continue
@@ -173,7 +198,14 @@ def _worker(rank: int, world: int, args, port: int):
             best_acc = float(ck.get('best_acc', 0.0))
             iteration = int(ck.get('iteration', 0))
             if not args.reset_lr and 'optimizer' in ck:
-                ckpt.load_optimizer_state(eng, ck['optimizer'])  # restores the group's lr as optimizer.load_state_dict does
+                if groups is None:
+                    ckpt.load_optimizer_state(eng, ck['optimizer'])  # restores the group's lr as optimizer.load_state_dict does
+                else:
+                    saved = ck['optimizer']['param_groups']
+                    if [len(g['params']) for g in saved] != [len(ks) for ks, _ in groups]:
+                        raise ValueError("the checkpoint's optimizer groups are not those of --train_what %s" % args.train_what)
+                    ckpt.load_optimizer_state(eng, ck['optimizer'], names=[k for ks, _ in groups for k in ks])
+                    set_lr(1.0, saved=[float(g['lr']) for g in saved])
     allreduce = make_allreduce(dist, world)
     probe = getattr(args, '_probe', None)   # tests only: the rank leaves its arenas (and in test mode the totals) behind
     src_train = src_val = None
@@ -275,13 +307,15 @@ def _worker(rank: int, world: int, args, port: int):
             nv = max(n_val, 1)
             val_acc = va / nv
             log('Loss {:.4f}\t Acc: {:.4f} \t'.format(vl / nv, val_acc), flush=True)
-            eng.lr = base_lr * lr_multiplier(epoch, 0.1, milestones, 1)  # scheduler.step(epoch), eval/test.py:197
+            set_lr(lr_multiplier(epoch, 0.1, milestones, 1))  # scheduler.step(epoch), eval/test.py:197
             is_best = val_acc > best_acc  # eval/test.py:205-214
             best_acc = max(val_acc, best_acc)
             if rank == 0 and args.save_dir:
                 os.makedirs(args.save_dir, exist_ok=True)
                 state = {'epoch': epoch + 1, 'net': args.net, 'state_dict': {'module.' + k: v.cpu() for k, v in eng.state_dict().items()},
-                         'best_acc': best_acc, 'optimizer': ckpt.optimizer_state_dict(eng), 'iteration': iteration}
+                         'best_acc': best_acc, 'iteration': iteration,
+                         'optimizer': (ckpt.optimizer_state_dict(eng) if groups is None else
+                                       ckpt.grouped_optimizer_state_dict(eng, [g for g in eng.param_groups if not g['frozen']]))}
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
         log('Training from ep %d to ep %d finished' % (args.start_epoch, args.epochs))
         if probe:

@@ -1,15 +1,28 @@
-"""``dpc_amd.optim.Adam``: the reference's ``optim.Adam(params, lr=args.lr, weight_decay=args.wd)`` (dpc/main.py:80-81) as ONE fused
-kernel over the engine's flat arenas instead of torch's per-tensor update over 76 parameters.
+"""``dpc_amd.optim.Adam``: the reference's ``optim.Adam(params, lr=args.lr, weight_decay=args.wd)`` (dpc/main.py:80-81, eval/test.py:88)
+as ONE fused kernel over the engine's flat arenas instead of torch's per-tensor update over 76 parameters.
 
-    model = dpc_amd.model.DPC_RNN(...).to('cuda')
+    model = dpc_amd.model.DPC_RNN(...).to('cuda')                      # or dpc_amd.lc.LC(...)
     optimizer = dpc_amd.optim.Adam(model.parameters(), lr=1e-3, weight_decay=1e-5)
     ...
-    optimizer.zero_grad(); loss.backward(); optimizer.step()          # dpc/main.py:229-231, unchanged
+    optimizer.zero_grad(); loss.backward(); optimizer.step()          # dpc/main.py:229-231, eval/test.py:253-255, unchanged
 
-The parameters of ``DPC_RNN`` are views of the engine's parameter arena and, after ``loss.backward()``, their ``.grad`` are views of
-its gradient arena (dpc_amd/model.py), so ``step()`` is ``dpc_adam_dev`` over the arenas with torch.optim.Adam's arithmetic (L2
-weight decay added to the gradient, bias-corrected moments; tests/test_engine_gpu.py holds it to the reference's own Adam step).
-``state_dict()`` / ``load_state_dict()`` speak torch.optim.Adam's layout (dpc_amd/checkpoint.py), so checkpoints move both ways.
+The parameters of ``DPC_RNN`` / ``LC`` are views of the engine's parameter arena and, after ``loss.backward()``, their ``.grad`` are
+views of its gradient arena (dpc_amd/model.py, dpc_amd/lc.py), so ``step()`` is one launch over the arenas with torch.optim.Adam's
+arithmetic (L2 weight decay added to the gradient, bias-corrected moments; tests/test_engine_gpu.py holds it to the reference's own
+Adam step).
+
+Parameter groups: any partition of (a subset of) the module's parameters, each group with its own ``lr`` / ``weight_decay`` --
+``--train_what ft`` of eval/test.py:76-84 builds one group per parameter.  ``step()`` reads the groups' current values every time
+(``LambdaLR`` works) and maps them onto ``engine.set_param_groups``: the segment table of ``dpc_adam_groups_dev`` is re-uploaded
+only when a value changed.  A parameter that is in no group, or whose ``.grad`` is ``None`` (``requires_grad = False``, or unused),
+is frozen for that step -- neither read nor written, which is torch's skip.  With ONE group that holds every parameter, all with
+gradients, the step is ``dpc_adam_dev`` exactly as before.  One step counter serves all parameters: one that joins later is updated
+with the run's bias corrections, where torch would restart them (``BackboneEngine.set_param_groups``).
+
+``load_state_dict()`` wants the file's groups to match this optimizer's in number and sizes, as torch's does (the one-group
+optimizer used to read the file's first group whatever followed it).
+``state_dict()`` / ``load_state_dict()`` speak torch.optim.Adam's layout (dpc_amd/checkpoint.py) -- with groups: one ``param_groups``
+entry per group and state only for parameters that have been updated -- so checkpoints move both ways.
 The engine is created by the module's first forward; a step before that has nothing to update and raises.
 """
 from __future__ import annotations
@@ -26,21 +39,38 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("amsgrad is not supported (the reference does not use it, dpc/main.py:80-81)")
         if tuple(betas) != (0.9, 0.999) or eps != 1e-8:
             raise ValueError("dpc_amd.optim.Adam runs the reference's configuration: betas (0.9, 0.999), eps 1e-8")
+        params = list(params)
+        if params and isinstance(params[0], dict) and any(("betas" in g and tuple(g["betas"]) != (0.9, 0.999)) or g.get("eps", 1e-8) != 1e-8
+                                                          or g.get("amsgrad") for g in params):
+            raise ValueError("dpc_amd.optim.Adam runs the reference's configuration in every group: betas (0.9, 0.999), eps 1e-8, no amsgrad")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) != 1:
-            raise ValueError("one parameter group (the reference passes model.parameters(), dpc/main.py:74-78)")
+        for g in self.param_groups:
+            if g.get("amsgrad") or tuple(g["betas"]) != (0.9, 0.999) or g["eps"] != 1e-8:
+                raise ValueError("dpc_amd.optim.Adam runs the reference's configuration in every group: betas (0.9, 0.999), eps 1e-8, no amsgrad")
         self._pending_state = None
+        self._by_ptr = None     # (engine, {arena address: parameter name})
+        self._updated = set()   # names of the parameters that have been updated at least once (torch creates their state then)
 
     def _engine(self):
-        ps = self.param_groups[0]["params"]
+        ps = [p for g in self.param_groups for p in g["params"]]
         eng = engine_of(ps[0]) if ps else None
         if eng is None:
             raise RuntimeError("dpc_amd.optim.Adam: the parameters are not backed by an engine yet -- run a forward of the "
-                               "dpc_amd.model.DPC_RNN they belong to first (it moves them into the engine's arena)")
-        names = list(eng.PRM.keys())
-        if len(ps) != len(names) or any(p.data_ptr() != eng.PRM[k].data_ptr() for p, k in zip(ps, names)):
-            raise RuntimeError("dpc_amd.optim.Adam updates ALL parameters of one DPC_RNN in registration order (model.parameters())")
+                               "dpc_amd module (DPC_RNN / LC) they belong to first (it moves them into the engine's arena)")
+        if self._by_ptr is None or self._by_ptr[0] is not eng:
+            self._by_ptr = (eng, {t.data_ptr(): k for k, t in eng.PRM.items()})
+        by_ptr = self._by_ptr[1]
+        names = []
+        for g in self.param_groups:
+            ks = [by_ptr.get(p.data_ptr()) for p in g["params"]]
+            if any(k is None for k in ks):
+                raise RuntimeError("dpc_amd.optim.Adam updates parameters of ONE dpc_amd module (views of its engine's arena)")
+            names.append(ks)
         return eng, names
+
+    def _plain(self, eng, names) -> bool:
+        """one group holding every parameter in registration order: the one-group update, exactly as without groups"""
+        return len(names) == 1 and names[0] == list(eng.PRM.keys())
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -50,34 +80,63 @@ class Adam(torch.optim.Optimizer):
                 loss = closure()
         eng, names = self._engine()
         if self._pending_state is not None:
-            ckpt.load_optimizer_state(eng, self._pending_state)
+            self._load_into(eng, names, self._pending_state)
             self._pending_state = None
-        g = self.param_groups[0]
-        for p, k in zip(g["params"], names):
-            if p.grad is None:
-                raise RuntimeError(f"dpc_amd.optim.Adam: parameter {k} has no gradient (torch would skip it; the fused update covers "
-                                   "the whole arena) -- call loss.backward() first")
-            if p.grad.data_ptr() != eng.G[k].data_ptr():   # gradients that did not come from the engine's backward: bring them in
-                eng.G[k].copy_(p.grad)
-        eng.lr, eng.wd = float(g["lr"]), float(g["weight_decay"])
+        live = []
+        for g, ks in zip(self.param_groups, names):
+            have = []
+            for p, k in zip(g["params"], ks):
+                if p.grad is None:   # torch skips it: frozen for this step
+                    continue
+                if p.grad.data_ptr() != eng.G[k].data_ptr():   # gradients that did not come from the engine's backward: bring them in
+                    eng.G[k].copy_(p.grad)
+                have.append(k)
+            live.append(have)
+        if self._plain(eng, names) and live == names:
+            g = self.param_groups[0]
+            eng.set_param_groups(None)
+            eng.lr, eng.wd = float(g["lr"]), float(g["weight_decay"])
+        else:
+            if not any(live):
+                return loss   # nothing has a gradient: torch's step would do nothing either
+            eng.set_param_groups([{"params": have, "lr": float(g["lr"]), "weight_decay": float(g["weight_decay"])}
+                                  for g, have in zip(self.param_groups, live)])
         eng.adam_step()
+        self._updated.update(k for have in live for k in have)
         eng.packed_for_step = -1
         return loss
 
+    def _groups_for_state(self, names):
+        return [{"params": ks, "lr": float(g["lr"]), "weight_decay": float(g["weight_decay"])} for g, ks in zip(self.param_groups, names)]
+
     def state_dict(self):
         try:
-            eng, _ = self._engine()
+            eng, names = self._engine()
         except RuntimeError:
             return super().state_dict()   # nothing has run yet: torch's own (empty) state
-        return ckpt.optimizer_state_dict(eng)
+        if self._plain(eng, names) and (not self._updated or len(self._updated) == len(names[0])):
+            return ckpt.optimizer_state_dict(eng)
+        return ckpt.grouped_optimizer_state_dict(eng, self._groups_for_state(names), self._updated)
+
+    def _load_into(self, eng, names, state_dict):
+        flat = [k for ks in names for k in ks]
+        ckpt.load_optimizer_state(eng, state_dict, names=flat)
+        ids = [i for g in state_dict["param_groups"] for i in g["params"]]
+        self._updated = {k for k, i in zip(flat, ids) if i in state_dict["state"]}
 
     def load_state_dict(self, state_dict):
-        g0 = state_dict["param_groups"][0]
-        self.param_groups[0]["lr"] = float(g0["lr"])
-        self.param_groups[0]["weight_decay"] = float(g0.get("weight_decay", 0.0))
+        saved = state_dict["param_groups"]
+        if len(saved) != len(self.param_groups) or any(len(a["params"]) != len(b["params"]) for a, b in zip(saved, self.param_groups)):
+            raise ValueError("loaded state dict has a different number of parameter groups, or a group of another size "
+                             "(torch.optim.Optimizer.load_state_dict raises the same way)")
+        for g, sg in zip(self.param_groups, saved):
+            g["lr"] = float(sg["lr"])
+            g["weight_decay"] = float(sg.get("weight_decay", 0.0))
+            if "initial_lr" in sg:
+                g["initial_lr"] = sg["initial_lr"]
         try:
-            eng, _ = self._engine()
+            eng, names = self._engine()
         except RuntimeError:
             self._pending_state = state_dict   # the engine does not exist yet: applied at the first step
             return
-        ckpt.load_optimizer_state(eng, state_dict)
+        self._load_into(eng, names, state_dict)

@@ -304,6 +304,23 @@ int dpc_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, 
 int dpc_step_advance(int32_t* step_dev, float* bias_corr_dev, double beta1, double beta2, dpc_stream_t stream);
 int dpc_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
                  float wd, const float* bias_corr_dev, float grad_scale, dpc_stream_t stream);
+/* Adam with parameter groups (torch.optim.Adam over several groups, eval/test.py:76-84): ONE launch over the flat arenas driven by a
+ * segment table in device memory.  Segments are sorted and non-overlapping, begin / end in floats and multiples of 4 (the arenas keep
+ * every tensor 16-byte aligned, so a 16-byte access never straddles two parameters); floats outside every segment are padding and
+ * are never touched.  active = 0: a frozen segment -- g, p, m, v are neither read nor written.  An active segment with lr = 0
+ * still updates m and v, as torch does.  Betas, eps, the device bias-correction pair and grad_scale are common to all segments and
+ * mean what they mean for dpc_adam_dev, whose per-element arithmetic this is.  n % 4 == 0, 16-byte aligned arenas,
+ * 1 <= n_segments <= DPC_ADAM_MAX_SEGMENTS; the table's contents are validated by whoever builds it (dpc_amd/engine.py). */
+#define DPC_ADAM_MAX_SEGMENTS 512
+typedef struct dpc_adam_segment {
+    int64_t begin, end;      /* floats, multiples of 4 */
+    float lr, weight_decay;
+    int32_t active;          /* 0 = frozen */
+    int32_t reserved;
+} dpc_adam_segment;
+int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                        int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
+                        dpc_stream_t stream);
 /* counter_dev[0] += 1 on the stream: the dropout draw counter (one draw per train-mode forward; the `step_dev` the recurrence and
  * the classifier head key their Philox masks on), graph-capturable like dpc_step_advance */
 int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream);
@@ -371,7 +388,10 @@ int dpc_gru_chain_bwd(const dpc_gru_chain_desc* c, dpc_stream_t stream);
  *  - the head (model_3d_lc.py:58-64, eval/test.py:244-255): spatial mean of the last ConvGRU state -> BatchNorm1d ->
  *    Dropout(p) -> Linear -> CrossEntropyLoss + top-1, forward and backward.  result[0..1] = mean loss, accuracy.
  *    dpc_lc_head_bwd takes the Dropout keep values from where the forward took them (drop_mask, else the Philox draw of
- *    (seed, step_dev[0]), else 1): call it with the descriptor of the train-mode forward, before step_dev advances. */
+ *    (seed, step_dev[0]), else 1): call it with the descriptor of the train-mode forward, before step_dev advances.
+ *    It starts from whatever `dlogits` holds: the forward leaves the mean cross-entropy's gradient there; a caller that
+ *    differentiates something else (torch autograd through LC.forward) overwrites it with its d loss / d logits and passes its
+ *    d loss / d context in d_bn_out. */
 int dpc_bn_finalize_running(const float* partials, int32_t rows, int32_t C, double count, const float* gamma, const float* beta,
                             float eps, float* mean, float* invstd, float* scale, float* shift, float* running_mean,
                             float* running_var, int64_t* num_batches_tracked, float momentum, dpc_stream_t stream);
@@ -402,6 +422,8 @@ typedef struct dpc_lc_head_desc {
     float *g_fc_weight, *g_fc_bias, *g_bn_weight, *g_bn_bias;
     float* dctx;                  /* [B][D] scratch */
     float* d_hlast;               /* [B*SQ][D] f32: seed of dpc_gru_chain_bwd */
+    const float* d_bn_out;        /* optional [B][D] f32: an upstream gradient at bn_out (LC.forward's `context`, the BatchNorm1d output
+                                     before Dropout), added to dy * keep ahead of the BatchNorm backward; NULL = none */
 } dpc_lc_head_desc;
 int dpc_lc_head_fwd(const dpc_lc_head_desc* c, dpc_stream_t stream);
 int dpc_lc_head_bwd(const dpc_lc_head_desc* c, dpc_stream_t stream);
