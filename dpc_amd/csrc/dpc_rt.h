@@ -230,7 +230,11 @@ template <> __device__ __forceinline__ f32x16 mfma_unit<bf16_t>(const u32x4& a, 
 
 // ---- "bf16x6": f32 operands on the bf16 matrix pipe at f32-grade accuracy (round 4; profiles/r04_bf16x3_feasibility.txt).
 // x = x1 + x2 + x3 with x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2) (24 mantissa bits in three pieces); a product
-// keeps the six terms a_i b_j with i + j <= 4 -- everything down to 2^-24 |a||b| -- accumulated in f32, smallest first.
+// keeps the six terms a_i b_j with i + j <= 4 -- each worth 2^-16 |a||b| or more; the three left out are 2^-24 |a||b| and less --
+// accumulated in f32, smallest first.  The split is not what a result is off by, the f32 accumulator is: measured on an MI355X
+// against f64 over reductions of 576 (tests/x6_cases.py), rel-L2 3.2e-7 .. 3.5e-7 on random operands (the f32 MFMA chain:
+// 3.9e-7 .. 4.1e-7) and at most 6.9e-7 of sum |a||b| per element on positive operands (the chain: 3.2e-6; it rounds after every
+// product, v_mfma_f32_32x32x16_bf16 after the eight products of a lane half).  One of the six terms missing costs 2.3e-6 .. 3.8e-6.
 // Six v_mfma_f32_32x32x16_bf16 (32 cycles each) replace eight v_mfma_f32_32x32x2_f32 (64 cycles each) per K = 16: 2.7x the f32
 // matrix rate.  Measured against the reference's fp32 scores on the CPU model of this arithmetic: 1.1e-4 .. 1.7e-4 (the two-piece
 // "bf16x3" misses north_star's 1e-3: 1.0e-3 .. 2.5e-3).  Two 16-byte units (8 f32, K index = the element order) per operand.

@@ -138,9 +138,15 @@ int dpc_set_reserved_cus(int32_t n);
 
 /* Arithmetic of the f32 kernels' contractions (dtype_in == DPC_F32 in dpc_conv_igemm / dpc_conv_wgrad / dpc_gemm_nt_splitk):
  *   0  exact f32 MFMA chains (v_mfma_f32_32x32x2_f32, 157 TFLOP/s peak) -- the default, bitwise an fmaf chain;
- *   1  "bf16x6": each f32 operand split into three bf16 pieces in registers, the six products down to 2^-24 on the bf16 matrix
- *      pipe, f32 accumulation -- f32-grade results (score within 2e-4 of the reference's fp32 CPU path, north_star asks 1e-3) at up
- *      to 2.7x the f32 matrix rate.  Operands, activations and outputs stay f32 in HBM.
+ *   1  "bf16x6": each f32 operand split into three bf16 pieces in registers, the six piece products of 2^-16 |a||b| and more on
+ *      the bf16 matrix pipe (the three left out are 2^-24 |a||b| and less), f32 accumulation -- f32-grade results (score within
+ *      2e-4 of the reference's fp32 CPU path, north_star asks 1e-3) at up to 2.7x the f32 matrix rate.  Operands, activations and
+ *      outputs stay f32 in HBM.  What a result is off by is the f32 accumulator's rounding, not the split: measured on an MI355X
+ *      against f64 over reductions of 576, rel-L2 3.2e-7 .. 3.5e-7 on random operands (mode 0: 3.9e-7 .. 4.1e-7) and at most
+ *      6.9e-7 of sum |a||b| per element on positive operands (mode 0: 3.2e-6 -- the fmaf chain rounds the accumulator after
+ *      every product, the bf16 MFMA after every eight); one missing piece product would cost 2.3e-6 .. 3.8e-6
+ *      (tests/x6_cases.py).  conv_halo_kernel<float,...> (f32 1x3x3 convs over 32 channels) has no bf16x6 form and runs mode 0
+ *      under either setting.
  * Process-wide host state read when a launch is planned; returns the previous mode. */
 int dpc_set_f32_matmul(int32_t mode);
 

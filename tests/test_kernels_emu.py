@@ -362,7 +362,9 @@ def x6(k):
 
 def test_f32_kernels_in_bf16x6_arithmetic(k, x6):
     """every f32 contraction kernel with its operands split three ways onto the bf16 matrix pipe: same cases, same f32 tolerances
-    (1e-4 of max-abs for the convolutions, 1e-5 for the GEMMs against f64) -- the split keeps the products down to 2^-24"""
+    (1e-4 of max-abs for the convolutions, 1e-5 for the GEMMs against f64).  These tolerances only say that the switch breaks
+    nothing: a kernel that ran three of the six piece products would pass them.  That all six are there is held term by term by
+    tests/x6_cases.py (tests/test_x6_emu.py, tests/test_x6_gpu.py)"""
     kc.case_conv_fwd(k, F32, 2, 16, 64, 2, 9, 9, (1, 3, 3), (1, 2, 2), (0, 1, 1))
     kc.case_conv_fwd(k, F32, 1, 32, 32, 3, 6, 6, (3, 3, 3), (1, 1, 1), (1, 1, 1))
     kc.case_conv_dgrad(k, F32, 2, 16, 64, 5, 8, 8, (3, 3, 3), (2, 2, 2), (1, 1, 1))
