@@ -268,7 +268,7 @@ int dpc_tpool_split_bwd(const void* x, const void* d_relu, const float* d_inf, i
 /* ---- pieces around the fused ConvGRU recurrence (dpc_gru_chain_* below) -------------------
  * colsum of [M][D] (leading dimension ld) into out[D] (+= when accumulate): bias gradients of the ConvGRU / network_pred */
 int dpc_colsum(const void* x, int32_t dtype, int32_t ld, int32_t M, int32_t D, float* out, int32_t accumulate,
-               float* ws, int64_t ws_floats /* >= 64*D */, dpc_stream_t stream);
+               float* ws, int64_t ws_floats /* >= min(ceil(M/256), 64)*D; 64*D always suffices */, dpc_stream_t stream);
 
 /* ---- contrastive loss head (dpc/main.py:178-185,213-218; utils/utils.py:38-55) -------
  * mask: closed form of dpc/model_3d.py:86-96, int8 [B][P][SQ][B][P][SQ] contiguous.

@@ -38,7 +38,7 @@ def case_lc_head_upstream(k: kc.K, dtype, B, SQ, D, NC, report=print):
     k.call("dpc_lc_head_bwd", C.byref(d))
     k.sync()
     ce = {n: t[n].cpu().clone() for n in QUANTITIES + ("dctx",)}
-    zero = k.zeros(B, D)
+    zero = k.zeros(B, D)   # real input: an upstream gradient of +0
     d.d_bn_out = zero.data_ptr()
     k.call("dpc_lc_head_bwd", C.byref(d))
     k.sync()

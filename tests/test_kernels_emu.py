@@ -250,6 +250,13 @@ def test_pack3d_multi(k, dtype):
     kc.case_pack3d_multi(k, dtype, [(24, 40, 9), (70, 8, 27), (16, 130, 1), (8, 8, 16), (3, 5, 70)])   # ragged tiles, 1x1, taps beyond the tile
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("mdl", [(1, 5, 8), (255, 256, 256), (257, 96, 96), (1000, 40, 768)])
+def test_colsum(k, dtype, mdl):
+    """dpc_colsum: the smallest shape, one row either side of a 256-row slice, a leading dimension beyond D (the G_all slices)"""
+    kc.case_colsum(k, dtype, *mdl)
+
+
 def test_philox_known_answers():
     """Random123 kat_vectors for philox4x32-10 pin the numpy generator the dropout-mask cases compare against"""
     import numpy as np

@@ -269,6 +269,14 @@ def test_pack3d_multi(k, dtype):
     kc.case_pack3d_multi(k, dtype, [(64, 64, 9), (128, 64, 9), (256, 128, 27), (512, 256, 27), (256, 128, 1), (70, 24, 27)])
 
 
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("mdl", [(1, 5, 8), (255, 256, 256), (257, 96, 96), (1000, 40, 768), (14336, 768, 768), (16385, 256, 256)])
+def test_colsum(k, dtype, mdl):
+    """dpc_colsum: the simulator tier's shapes, the engine's ConvGRU bias gradient at cfg2 (7 steps x 2 048 rows, three gates of
+    256), and one row past 64 slices of 256 (the slice cap, ragged last slice)"""
+    kc.case_colsum(k, dtype, *mdl)
+
+
 def test_dropout_mask(k):
     kc.case_dropout_mask(k, 1027, 0.1, 233, 0)
     kc.case_dropout_mask(k, 7 * 2048 * 256, 0.1, (5 << 32) | 77, 12)  # cfg2: masks of all 7 recurrence steps
