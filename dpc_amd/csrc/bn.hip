@@ -303,6 +303,7 @@ extern "C" int dpc_bn_apply(const void* x, void* y, int32_t dtype, int64_t rows,
     const bool fixed = (256 * E) % C == 0;
     static const int rev_on = getenv("DPC_BN_APPLY_REV") ? atoi(getenv("DPC_BN_APPLY_REV")) : 0;
     const int rev = rev_on && bn_streaming(units) ? 1 : 0;   // small tensors fit the caches whole: the order does not matter
+    if (rev && (dtype == DPC_F32 || dtype == DPC_BF16)) dpc_plan_detail("rev");   // an off-default arm shows in dpc_last_kernel
     if (dtype == DPC_F32) {
         if (fixed) {
             if (bn_streaming(units)) { DPC_LAUNCH((bn_apply_kernel<float, true, true>), dim3(grid_for(units)), dim3(256), stream, (const float*)x, (float*)y, units, C, scale, shift, (const float*)res, rscale, rshift, relu, mask, rev); } else { DPC_LAUNCH((bn_apply_kernel<float, true, false>), dim3(grid_for(units)), dim3(256), stream, (const float*)x, (float*)y, units, C, scale, shift, (const float*)res, rscale, rshift, relu, mask, rev); }

@@ -997,7 +997,8 @@ static int ws_enabled() { static int v = env_int("DPC_IGEMM_WS", 1); return v; }
 static int ws_min_rows() { static int v = env_int("DPC_IGEMM_WS_MINROWS", 256 * 64); return v; }
 static int ws_max_programs() { static int v = env_int("DPC_IGEMM_WS_GM", 256); return v; }
 
-static bool ws_plan(const dpc_conv_desc* d, WsParams* p) {
+// tg_declined: set when DPC_IGEMM_WS_TGROUP=0 keeps a shape off the temporally grouped tiles it would otherwise take
+static bool ws_plan(const dpc_conv_desc* d, WsParams* p, bool* tg_declined = nullptr) {
     if (!ws_enabled()) return false;
     if (d->dtype_in != DPC_BF16 || d->dtype_out != DPC_BF16) return false;
     if (d->Co < 64 || d->Co % 8 || d->ldo % 8 || d->ldw % 8) return false;
@@ -1041,7 +1042,9 @@ static bool ws_plan(const dpc_conv_desc* d, WsParams* p) {
     {
         static const int tg_on = env_int("DPC_IGEMM_WS_TGROUP", 1);
         const int hw = g.RH * g.RW;
-        if (tg_on && !p->parity && g.KT > 1 && unit_strides && g.RT == g.ST && g.RT > 1) {
+        const bool tg_shape = !p->parity && g.KT > 1 && unit_strides && g.RT == g.ST && g.RT > 1;
+        if (tg_declined) *tg_declined = tg_shape && !tg_on;
+        if (tg_on && tg_shape) {
             p->tgroup = 1; p->hw = hw; p->d_hw = make_fastdiv((uint32_t)hw);
             p->nclip = g.M / (g.RT * hw);
             p->tpt = (int)(((long long)p->nclip * hw + 255) / 256);
@@ -1062,6 +1065,7 @@ static bool ws_plan(const dpc_conv_desc* d, WsParams* p) {
 
 // igemm_wsd_kernel: bf16 input-gradient of a 1 x 3 x 3 convolution with stride (1, 2, 2), pad (0, 1, 1) from 128 to 64 channels over
 // 16 x 16 gradient planes (32 x 32 output planes).  p->gm / p->ntn = workgroups of kind A / B, p->ntm = planes.
+static int wsd_a_share() { static int v = env_int("DPC_WSD_A_PERMILLE", 556); return v; }
 static bool wsd_plan(const dpc_conv_desc* d, WsParams* p) {
     static const int on = env_int("DPC_IGEMM_WSD", 1);
     if (!on || !ws_enabled()) return false;
@@ -1081,7 +1085,7 @@ static bool wsd_plan(const dpc_conv_desc* d, WsParams* p) {
     p->wgt_bytes = (unsigned)(((long long)(d->Co - 1) * d->ldw + 9 * 128) * 2);
     p->ntm = (int)planes;
     // kind A walks 4 shifts x 2 groups = 8 chunks per plane, kind B 6, and both pay one epilogue (~2 chunks' worth): 10 : 8
-    static const int a_share = env_int("DPC_WSD_A_PERMILLE", 556);
+    const int a_share = wsd_a_share();
     const int wgs = dpc_persistent_grid(ws_max_programs());
     int gma = (int)((long long)wgs * a_share / 1000);
     if (gma < 1) gma = 1;
@@ -1104,10 +1108,12 @@ int dpc_conv_ws_try(const dpc_conv_desc* d, const void* src, const void* wgt, vo
     if (!addend && !stats && !epi_any(epi) && wsd_plan(d, &p)) {
         if (((uintptr_t)out % 16) || ((uintptr_t)src % 16) || ((uintptr_t)wgt % 16)) return 1;
         p.src = src; p.wgt = wgt; p.out = out; p.addend = nullptr; p.stats = nullptr; p.dbg = 0;
+        if (wsd_a_share() != 556) dpc_plan_detail("a=%d", wsd_a_share());   // an off-default arm shows in dpc_last_kernel
         DPC_LAUNCH(igemm_wsd_kernel, dim3((unsigned)(p.gm + p.ntn)), dim3(512), stream, p);
         return dpc_launch_status();
     }
-    if (!ws_plan(d, &p)) return 1;
+    bool tg_declined = false;
+    if (!ws_plan(d, &p, &tg_declined)) return 1;
     if (epi_any(epi)) return 1;  // the fused backward pieces of dpc_conv_igemm_ex are not built into these kernels (yet)
     if (addend && stats) return 1;  // not a combination of this path: the generic kernel serves it
     if (p.parity && (addend || stats)) return 1;
@@ -1119,6 +1125,7 @@ int dpc_conv_ws_try(const dpc_conv_desc* d, const void* src, const void* wgt, vo
     p.dbg = 0;
 #endif
     dim3 grid((unsigned)(p.gm * p.ntn)), block(512);
+    if (tg_declined) dpc_plan_detail("tgroup=0");
     if (p.parity) {
         DPC_LAUNCH((igemm_ws_kernel<false, true>), grid, block, stream, p);
     } else if (p.plane) {

@@ -421,10 +421,12 @@ extern "C" int dpc_pack_input_s2d(const float* block, void* out, int32_t dtype_o
     if ((H & 1) || (W & 1)) return DPC_ERR_UNSUPPORTED;
     const long long cells = (long long)BN * T * (H / 2) * (W / 2);
     static const int rev = getenv("DPC_PACK_REV") ? atoi(getenv("DPC_PACK_REV")) : 0;
+    static const int cap = getenv("DPC_PACK_GRID") ? atoi(getenv("DPC_PACK_GRID")) : 16384;  // test tiers shrink it: several sweeps on small shapes
+    if (rev && (dtype_out == DPC_F32 || dtype_out == DPC_BF16)) dpc_plan_detail("rev");   // an off-default arm shows in dpc_last_kernel
     if (dtype_out == DPC_F32) {
-        DPC_LAUNCH((pack_input_s2d_kernel<float>), dim3(grid_for(cells, 256, 16384)), dim3(256), stream, block, (float*)out, BN, T, H, W, rev);
+        DPC_LAUNCH((pack_input_s2d_kernel<float>), dim3(grid_for(cells, 256, cap)), dim3(256), stream, block, (float*)out, BN, T, H, W, rev);
     } else if (dtype_out == DPC_BF16) {
-        DPC_LAUNCH((pack_input_s2d_kernel<bf16_t>), dim3(grid_for(cells, 256, 16384)), dim3(256), stream, block, (bf16_t*)out, BN, T, H, W, rev);
+        DPC_LAUNCH((pack_input_s2d_kernel<bf16_t>), dim3(grid_for(cells, 256, cap)), dim3(256), stream, block, (bf16_t*)out, BN, T, H, W, rev);
     } else {
         return DPC_ERR_ARG;
     }

@@ -101,10 +101,12 @@ extern "C" int dpc_bn_relu_maxpool_fwd(const void* x, int32_t dtype, int32_t NT,
     static const int rev = getenv("DPC_POOL_FWD_REV") ? atoi(getenv("DPC_POOL_FWD_REV")) : 0;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     const long long units = (long long)NT * Ho * Wo * (C / E);
+    static const int cap = getenv("DPC_POOL_FWD_GRID") ? atoi(getenv("DPC_POOL_FWD_GRID")) : 16384;  // test tiers shrink it: several sweeps on small shapes
+    if (rev && (dtype == DPC_F32 || dtype == DPC_BF16)) dpc_plan_detail("rev");   // an off-default arm shows in dpc_last_kernel
     if (dtype == DPC_F32) {
-        DPC_LAUNCH((bn_relu_maxpool_fwd_kernel<float>), dim3(grid_for(units)), dim3(256), stream, (const float*)x, NT, H, W, C, Ho, Wo, scale, shift, (float*)y, argmax, rev);
+        DPC_LAUNCH((bn_relu_maxpool_fwd_kernel<float>), dim3(grid_for(units, 256, cap)), dim3(256), stream, (const float*)x, NT, H, W, C, Ho, Wo, scale, shift, (float*)y, argmax, rev);
     } else if (dtype == DPC_BF16) {
-        DPC_LAUNCH((bn_relu_maxpool_fwd_kernel<bf16_t>), dim3(grid_for(units)), dim3(256), stream, (const bf16_t*)x, NT, H, W, C, Ho, Wo, scale, shift, (bf16_t*)y, argmax, rev);
+        DPC_LAUNCH((bn_relu_maxpool_fwd_kernel<bf16_t>), dim3(grid_for(units, 256, cap)), dim3(256), stream, (const bf16_t*)x, NT, H, W, C, Ho, Wo, scale, shift, (bf16_t*)y, argmax, rev);
     } else {
         return DPC_ERR_ARG;
     }

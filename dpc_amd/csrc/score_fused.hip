@@ -596,6 +596,7 @@ int dpc_score_gemm_try(const dpc_conv_desc* d, const void* src, const void* wgt,
     p.nsplit = (p.ntiles + p.tiles_per_split - 1) / p.tiles_per_split;
     const dim3 grid(nrb, p.nsplit);
     const size_t lds = 2 * (size_t)((p.D * 2 + 127) / 128) * BN * 128;
+    if (slots != 512) dpc_plan_detail("wgs=%d", slots);   // an off-default arm shows in dpc_last_kernel
     if (p.D == 256) {
         if (int e = allow_lds(score_gemm_kernel<16>, lds)) return e;
         DPC_LAUNCH_DYN((score_gemm_kernel<16>), grid, dim3(256), lds, stream, p);

@@ -360,6 +360,7 @@ def case_conv_wgrad(k: K, dtype, N, Ci, Co, T, H, W, ks, st, pd, seed=2, expect=
         gm = gw.clone()
         gm[:, :, ks[0] // 2, ks[1] // 2, ks[2] // 2] = 0
         rejects_dropped_tap(dw, gw, gm, 1e-4)
+    return ns.value   # slabs the planner chose (tests/switch_cases.py holds the split-K switches to it)
 
 
 def case_gemm_nt(k: K, dtype, M, N, Kd, seed=3, expect=None):
@@ -480,6 +481,7 @@ def case_stem(k: K, dtype, BN, T, H, W, Co=64, seed=4, expect=(None, None)):
     k.sync()
     all_finite(part, dw)
     assert relerr(dw, gw) < 1e-4
+    return ns.value
 
 
 # ------------------------------------------------------------------ batch norm

@@ -27,8 +27,8 @@ def nchw(t):  # engine activation [N,T,H,W,C] -> [N,C,T,H,W]
     return t.permute(0, 4, 1, 2, 3).contiguous()
 
 
-def _filled(net, size, B):
-    e = DPCEngine(net, size, 8, 5, 3, B, DEV, torch.bfloat16)
+def _filled(net, size, B, **kw):
+    e = DPCEngine(net, size, 8, 5, 3, B, DEV, torch.bfloat16, **kw)
     e.load_params(O.init_params_reference_style(net, seed=0))
     x = O.make_input_pcg(B, 8, 5, size).to(DEV)
     e.forward(x, train=False)   # fills every block's saved tensors (x_in, raw, act1, masks, statistics)
@@ -49,9 +49,49 @@ def eng34():
     return _filled("resnet34", 224, 4)
 
 
+@pytest.fixture(scope="module")
+def eng_nofold():
+    # DPC_FOLD=0 through the fold= argument: no fused backward epilogues, a masked dz copy and standalone reductions
+    return _filled("resnet18", 128, 16, fold=False)
+
+
+@pytest.fixture(scope="module")
+def eng_nofoldred():
+    # DPC_FOLD_RED=0 (read when the engine plans its backward): the gated addend stays fused, the reductions are their own launches
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("DPC_FOLD_RED", "0")
+        return _filled("resnet18", 128, 16)
+
+
 @pytest.mark.parametrize("bi", [0, 1, 2, 3, 4, 5, 6, 7])
 def test_block_backward_vs_rounding_oracle(eng, bi):
     _block_case(eng, bi)
+
+
+def _flags(e):
+    return [(b.fold_c1, b.gate, b.fold_prev) for b in e.blocks]
+
+
+def test_fold_switches_change_the_plan(eng, eng_nofold, eng_nofoldred):
+    """the two arms below run other code than the default engine: it folds each piece somewhere, they do not"""
+    dflt = _flags(eng)
+    for i, what in enumerate(("fold_c1", "gate", "fold_prev")):
+        assert any(f[i] for f in dflt), f"the default plan has no block with {what}: the arms would test nothing"
+    assert all(f == (False, False, False) for f in _flags(eng_nofold)), _flags(eng_nofold)
+    red = _flags(eng_nofoldred)
+    assert not any(f[0] or f[2] for f in red), red
+    assert [f[1] for f in red] == [f[1] for f in dflt], (red, dflt)
+
+
+# layer1.0 / .1 (fold_prev in the default plan), layer2.0 (strided + downsample) / .1, layer4.1 (no final ReLU)
+@pytest.mark.parametrize("bi", [0, 1, 2, 3, 7])
+def test_block_backward_vs_rounding_oracle_without_folding(eng_nofold, bi):
+    _block_case(eng_nofold, bi)
+
+
+@pytest.mark.parametrize("bi", [0, 1, 2, 3, 7])
+def test_block_backward_vs_rounding_oracle_without_folded_reductions(eng_nofoldred, bi):
+    _block_case(eng_nofoldred, bi)
 
 
 # one block of every kind r34 / 224^2 has: layer1.0 / .1 (fold_prev) / .2, layer2.0 (strided + downsample) / .1 / .3, layer3.0 / .1 / .5,
