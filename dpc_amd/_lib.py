@@ -112,6 +112,7 @@ _SIGS = {
     "dpc_transpose2d": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp],
     "dpc_pack_input_s2d": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "dpc_synthetic_input": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _vp, _vp],
+    "dpc_synthetic_labels": [_vp, _i32, _i32, C.c_uint64, _vp, _vp],
     "dpc_pack_stem_weight": [_vp, _vp, _i32, _i32, _vp],
     "dpc_unpack_stem_wgrad": [_vp, _i32, _vp, _i32, _vp],
     "dpc_bn_finalize": [_vp, _i32, _i32, _f64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp],

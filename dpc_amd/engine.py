@@ -22,7 +22,7 @@ reference's state_dict layout and are repacked (K-contiguous, compute dtype) onc
 per optimizer step.
 
 In file order: KernelTimer and the cost model; the conv unit and the block; ``BackboneEngine``, what the DPC-RNN step and the
-LC classifier (lc.LCEngine) share; ``DPCEngine``: the contrastive head, then the captured steps.
+LC classifier (lc.LCEngine) share, the capture machinery of their replayed steps included; ``DPCEngine``: the contrastive head, then its captured steps.
 """
 from __future__ import annotations
 
@@ -541,7 +541,11 @@ class BackboneEngine:
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
         self.timer: Optional["KernelTimer"] = None
         self._tag: Optional[str] = None
-        self._capture_events: Optional[list] = None   # fork / join events of the capture in progress (DPCEngine._capture)
+        self._capture_events: Optional[list] = None   # fork / join events of the capture in progress (_capture)
+        self._captures: Dict[tuple, object] = {}   # capture_train_step / capture_eval_step results by (input buffer, exchange, carve-out, ...)
+        self._capture_graphs: list = []            # their _Capture records; parked in _LIVE_GRAPHS when the engine goes (see there)
+        self._launches = 0                         # kernel launches issued through call() so far (_capture: launches per captured graph)
+        weakref.finalize(self, _park_graphs, self._capture_graphs)
         self._carved = False   # a CU carve-out for RCCL is in force (_backbone_backward sets it, _uncarve lifts it)
 
         # ---- flat f32 arenas: parameters, gradients, Adam moments
@@ -759,6 +763,7 @@ class BackboneEngine:
         self.need_part(ns.value * Co * K)
 
     def call(self, name, *args):
+        self._launches += 1
         if getattr(self.lib, "_f32_mode", 0) != self._x6:   # process-wide library state, read when a launch is planned: keep it ours
             self.lib.call("dpc_set_f32_matmul", self._x6)
             self.lib._f32_mode = self._x6
@@ -1040,7 +1045,7 @@ class BackboneEngine:
         values merged into one segment, and uploaded here -- only when a host value differs from what the device holds, so an lr
         schedule that calls this once per epoch costs one small copy per change and a caller that passes the same values every
         step costs none.  Never call it while a graph is being captured (the upload is a host-to-device copy).  The table lives in
-        one device buffer whose address never changes; a captured step (DPCEngine.capture_train_step) counts the table among the
+        one device buffer whose address never changes; a captured step (capture_train_step) counts the table among the
         values baked into it, so a replay after the groups changed raises instead of stepping with another table.
 
         ONE step counter serves all groups: a parameter that is frozen for the first k steps and trained afterwards is updated
@@ -1137,6 +1142,107 @@ class BackboneEngine:
             if allreduce is not None:
                 allreduce(self.flat_g)
 
+    # ------------------------------------------------------------------ captured steps: what both heads' capture_* share
+    def _baked_scalars(self) -> tuple:
+        """host scalars a captured step carries as kernel arguments (a replay keeps the values of its capture)"""
+        gd = self.gru_desc
+        base = (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
+        # with parameter groups the captured update reads the segment table: its contents belong to what a replay must still find
+        return base + ((self._seg_n, self._seg_host),) if self._groups else base
+
+    def check_graph_capture(self):
+        """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
+        if self.device.type != "cuda":
+            raise L.DpcError("hipGraph capture needs the HIP device")
+
+    def _capture(self, key: tuple, what: str, again: str, warm, body, run, refill=None, **attrs):
+        """what capture_train_step and capture_eval_step share: the cache by `key`, the eager `warm()` and the capture of
+        `body(cut)` on a side stream -- `cut()` ends one graph and begins the next where a replay has host work to do between
+        them --, the fork / join events, and ``replay()``, which checks the baked scalars and returns ``run(engine, graphs)``.
+        `attrs` are hung on the replay closure beside .graphs / .events / .refill / .kernels (kernel launches captured into each
+        graph: a capture that would leave an empty graph raises)."""
+        self.check_graph_capture()
+        hit = self._captures.get(key)
+        if hit is not None:   # the same static buffer, the same exchange: the capture that exists (see _LIVE_GRAPHS)
+            return hit
+        cur = torch.cuda.current_stream(self.device)
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):  # eager warm-up: lazy buffers, RCCL communicator
+            warm()
+        cur.wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        pool = torch.cuda.graph_pool_handle()
+        graphs: List[torch.cuda.CUDAGraph] = []
+        kernels: List[int] = []
+        state = {}
+
+        def begin():
+            state["g"] = torch.cuda.CUDAGraph()
+            state["g"].capture_begin(pool=pool)
+            state["n0"] = self._launches
+
+        def end():
+            state["g"].capture_end()
+            graphs.append(state["g"])
+            kernels.append(self._launches - state["n0"])
+
+        def cut(*_):
+            end()
+            begin()
+
+        side.wait_stream(cur)
+        # The fork / join events side() records while the step is being captured live as long as the graphs do (they hang off the
+        # replay closure): a captured event that is destroyed before its graph is the one candidate mechanism found for the host-memory
+        # corruption that used to follow graph destruction (see _LIVE_GRAPHS; DPC_KEEP_CAPTURE_EVENTS=0 lets them go when side()
+        # returns, as rounds 3-4 did -- the A/B of scripts/gpu_r5_graph_destroy.sh).
+        keep_events = os.environ.get("DPC_KEEP_CAPTURE_EVENTS", "1") != "0"
+        self._capture_events = [] if keep_events else None
+        try:
+            with torch.cuda.stream(side):
+                begin()
+                self.packed_for_step = -1
+                if refill is not None:
+                    refill()
+                body(cut)
+                end()
+        finally:
+            events, self._capture_events = self._capture_events, None
+        self.packed_for_step = -1   # the capture executed nothing: the packed weights are not those of this step yet
+        cur.wait_stream(side)
+        me = weakref.ref(self)   # the cached closure must not keep its engine (tens of GB of buffers) alive through a cycle
+        baked = self._baked_scalars()
+
+        def replay():
+            eng = me()
+            if eng is None:
+                raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
+            if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
+                raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
+                                   f"call {again}")
+            return run(eng, graphs)
+
+        replay.graphs = graphs
+        replay.kernels = kernels
+        replay.events = events   # destroyed after the graphs, not before
+        replay.refill = refill
+        for k, v in attrs.items():
+            setattr(replay, k, v)
+        self._capture_graphs.append(_Capture(graphs, events))
+        if not all(kernels):   # (parked like every other capture; never cached, never replayed)
+            raise L.DpcError(f"the captured {what} step was cut into an empty hipGraph (kernel launches per graph: {kernels})")
+        self._captures[key] = replay
+        return replay
+
+    def release_captures(self):
+        """forget this engine's captured train steps (the next capture_train_step captures again).  The hipGraphs are parked until the
+        interpreter exits, not destroyed -- see _LIVE_GRAPHS for why and for what that costs; DPC_KEEP_GRAPHS=0 destroys them here,
+        after the device has gone idle."""
+        torch.cuda.synchronize(self.device)
+        self._captures.clear()
+        _park_graphs(list(self._capture_graphs))
+        self._capture_graphs.clear()
+
 
 class DPCEngine(BackboneEngine):
     """the DPC-RNN step: backbone + ConvGRU aggregate / predict, contrastive score, loss, and the captured steps"""
@@ -1148,9 +1254,6 @@ class DPCEngine(BackboneEngine):
                  fold: bool | None = None, reserve_cus: int | None = None, f32_matmul: str | None = None):
         self.P = pred_step
         self.score_mode = "materialised"  # what the last train step ran ("fused": no [R][R] tensor in HBM)
-        self._captures: Dict[tuple, object] = {}   # capture_train_step results by (input buffer, exchange, carve-out)
-        self._capture_graphs: list = []            # their _Capture records; parked in _LIVE_GRAPHS when the engine goes (see there)
-        weakref.finalize(self, _park_graphs, self._capture_graphs)
         super().__init__(param_shapes(network, widths), network, sample_size, num_seq, seq_len, batch, device, compute_dtype, widths, lib,
                          lr, wd, dropout, seed, stem_fused, fold, reserve_cus, f32_matmul)
         self._build_head(score_path)
@@ -1360,88 +1463,6 @@ class DPCEngine(BackboneEngine):
         self.call("dpc_colsum", self.dP1, dc, D, P * M, D, Gm["network_pred.0.bias"], 0, self.part, self.part.numel())
         self.call("dpc_colsum", self.dP2, dc, D, P * M, D, Gm["network_pred.2.bias"], 0, self.part, self.part.numel())
 
-    def _baked_scalars(self) -> tuple:
-        """host scalars a captured step carries as kernel arguments (a replay keeps the values of its capture)"""
-        gd = self.gru_desc
-        base = (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
-        # with parameter groups the captured update reads the segment table: its contents belong to what a replay must still find
-        return base + ((self._seg_n, self._seg_host),) if self._groups else base
-
-    def check_graph_capture(self):
-        """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
-        if self.device.type != "cuda":
-            raise L.DpcError("hipGraph capture needs the HIP device")
-
-    def _capture(self, key: tuple, what: str, again: str, warm, body, run, refill=None, **attrs):
-        """what capture_train_step and capture_eval_step share: the cache by `key`, the eager `warm()` and the capture of
-        `body(cut)` on a side stream -- `cut()` ends one graph and begins the next where a replay has host work to do between
-        them --, the fork / join events, and ``replay()``, which checks the baked scalars and returns ``run(engine, graphs)``.
-        `attrs` are hung on the replay closure beside .graphs / .events / .refill."""
-        self.check_graph_capture()
-        hit = self._captures.get(key)
-        if hit is not None:   # the same static buffer, the same exchange: the capture that exists (see _LIVE_GRAPHS)
-            return hit
-        cur = torch.cuda.current_stream(self.device)
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):  # eager warm-up: lazy buffers, RCCL communicator
-            warm()
-        cur.wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        pool = torch.cuda.graph_pool_handle()
-        graphs: List[torch.cuda.CUDAGraph] = []
-        state = {}
-
-        def begin():
-            state["g"] = torch.cuda.CUDAGraph()
-            state["g"].capture_begin(pool=pool)
-
-        def cut(*_):
-            state["g"].capture_end()
-            graphs.append(state["g"])
-            begin()
-
-        side.wait_stream(cur)
-        # The fork / join events side() records while the step is being captured live as long as the graphs do (they hang off the
-        # replay closure): a captured event that is destroyed before its graph is the one candidate mechanism found for the host-memory
-        # corruption that used to follow graph destruction (see _LIVE_GRAPHS; DPC_KEEP_CAPTURE_EVENTS=0 lets them go when side()
-        # returns, as rounds 3-4 did -- the A/B of scripts/gpu_r5_graph_destroy.sh).
-        keep_events = os.environ.get("DPC_KEEP_CAPTURE_EVENTS", "1") != "0"
-        self._capture_events = [] if keep_events else None
-        try:
-            with torch.cuda.stream(side):
-                begin()
-                self.packed_for_step = -1
-                if refill is not None:
-                    refill()
-                body(cut)
-                state["g"].capture_end()
-                graphs.append(state["g"])
-        finally:
-            events, self._capture_events = self._capture_events, None
-        self.packed_for_step = -1   # the capture executed nothing: the packed weights are not those of this step yet
-        cur.wait_stream(side)
-        me = weakref.ref(self)   # the cached closure must not keep its engine (tens of GB of buffers) alive through a cycle
-        baked = self._baked_scalars()
-
-        def replay():
-            eng = me()
-            if eng is None:
-                raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
-            if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
-                raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
-                                   f"call {again}")
-            return run(eng, graphs)
-
-        replay.graphs = graphs
-        replay.events = events   # destroyed after the graphs, not before
-        replay.refill = refill
-        for k, v in attrs.items():
-            setattr(replay, k, v)
-        self._captures[key] = replay
-        self._capture_graphs.append(_Capture(graphs, events))
-        return replay
-
     def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
         """Captures the whole train step on `block` (a static device buffer: refill it in place between replays) into
         hipGraphs and returns ``replay() -> device f32[4]``.  One graph without data parallelism; with the two-bucket
@@ -1517,15 +1538,6 @@ class DPCEngine(BackboneEngine):
             return result
 
         return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
-
-    def release_captures(self):
-        """forget this engine's captured train steps (the next capture_train_step captures again).  The hipGraphs are parked until the
-        interpreter exits, not destroyed -- see _LIVE_GRAPHS for why and for what that costs; DPC_KEEP_GRAPHS=0 destroys them here,
-        after the device has gone idle."""
-        torch.cuda.synchronize(self.device)
-        self._captures.clear()
-        _park_graphs(list(self._capture_graphs))
-        self._capture_graphs.clear()
 
     def train_step(self, block: torch.Tensor, dropout_masks: Optional[torch.Tensor] = None, allreduce=None) -> torch.Tensor:
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""

@@ -81,6 +81,7 @@ class LCEngine(BackboneEngine):
         M = self.M
         self.d_hlast = self.empty((M, D), f32)
         self._ran_backbone_backward = True
+        self._eval_ran = False   # an eager eval-mode forward has run (test_video(graph=True) replays only after one)
         self.d_context = self.empty((B, D), f32)   # an upstream d loss / d context (backward's d_context) is staged here
         self.BUF["final_bn.running_mean"] = torch.zeros(D, dtype=f32, device=self.device)
         self.BUF["final_bn.running_var"] = torch.ones(D, dtype=f32, device=self.device)
@@ -130,16 +131,32 @@ class LCEngine(BackboneEngine):
         return out
 
     # ---- forward (model_3d_lc.py:47-65) + loss / accuracy (eval/test.py:244-255)
-    def forward(self, block: torch.Tensor, target: torch.Tensor, train: bool = False, gru_masks: Optional[torch.Tensor] = None,
-                fc_mask: Optional[torch.Tensor] = None):
-        """block [B,N,3,SL,H,W] f32, target [B] int64 class labels.  Returns (output [B,1,num_class], context [B,1,D]) as the
+    def set_labels(self, target: torch.Tensor):
+        """copy the class labels [B] of the next forward(block, None) / train_step(block, None) / captured step into ``self.target``
+        (eagerly: a host tensor is a host-to-device copy, so never inside a capture)"""
+        self.target.copy_(target.reshape(self.B).to(self.device, torch.int64))
+
+    def fill_synthetic(self, seed: int, block: Optional[torch.Tensor] = None):
+        """BackboneEngine.fill_synthetic (advances dev_input, draws the batch), then the batch's labels into ``self.target`` under the
+        same seed and the same draw counter (csrc/labels.hip).  Follow with forward(None, None, ...) / train_step(None, None).
+        Graph-safe: no host value changes between replays, the counter is read on the device."""
+        super().fill_synthetic(seed, block)
+        self.call("dpc_synthetic_labels", self.target, self.B, self.num_class, int(seed) & 0xFFFFFFFFFFFFFFFF, self.dev_input)
+
+    def forward(self, block: torch.Tensor, target: Optional[torch.Tensor] = None, train: bool = False,
+                gru_masks: Optional[torch.Tensor] = None, fc_mask: Optional[torch.Tensor] = None):
+        """block [B,N,3,SL,H,W] f32 (None: the stem's operand as it stands), target [B] int64 class labels (None: the labels as they
+        stand in ``self.target``: set_labels / fill_synthetic).  Returns (output [B,1,num_class], context [B,1,D]) as the
         reference does; ``self.result`` = device f32[2] (mean CE loss, top-1 accuracy).  gru_masks [N,M,D] / fc_mask [B,D]:
         optional explicit pre-scaled dropout masks (tests); train=True without them draws Philox masks in the kernels."""
         B, N, SQ, D, M = self.B, self.N, self.SQ, self.D, self.M
         if block is not None and (tuple(block.shape) != (B, N, 3, self.SL, self.size, self.size) or block.dtype != torch.float32):
             raise ValueError(f"block must be float32 [B,N,3,SL,H,W] = {(B, N, 3, self.SL, self.size, self.size)}")
         self.train_mode = bool(train)
-        self.target.copy_(target.reshape(B).to(self.device, torch.int64))
+        if target is not None:
+            self.set_labels(target)
+        if not train:
+            self._eval_ran = True   # the eval-mode forward has allocated what it allocates on first use (capture_eval_step's rule)
         x = self._backbone_forward(block)
         dc = L.dtype_code(self.cdtype)
         self.call("dpc_relu_tpool_fwd", x, dc, B, N, self.feat_shape[1], SQ, D, self.feat_relu)
@@ -218,12 +235,96 @@ class LCEngine(BackboneEngine):
         self.call("dpc_relu_tpool_bwd", self.blocks[-1].out, self.d_featrelu, dc, B, N, self.feat_shape[1], SQ, D, self.d_feat)
         self._backbone_backward(self.d_feat, on_tail_ready)
 
-    def train_step(self, block: torch.Tensor, target: torch.Tensor, allreduce=None, **masks) -> torch.Tensor:
-        """forward + CE / accuracy + backward (+ gradient all-reduce) + Adam; returns device f32[2] = loss, top-1"""
+    def train_step(self, block: torch.Tensor, target: Optional[torch.Tensor] = None, allreduce=None, **masks) -> torch.Tensor:
+        """forward + CE / accuracy + backward (+ gradient all-reduce) + Adam; returns device f32[2] = loss, top-1.
+        target=None: the labels as they stand in ``self.target``"""
         self.forward(block, target, train=True, **masks)
         self._backward_and_exchange(allreduce)
         self.adam_step()
         return self.result
+
+    # ---- captured steps (engine.BackboneEngine._capture): DPCEngine's contract on the classifier's step
+    def _baked_scalars(self) -> tuple:
+        hd = self.head_desc
+        return super()._baked_scalars() + (float(hd.p_drop), int(hd.seed))
+
+    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
+        """Captures forward(block, None, train=True) + backward + Adam into hipGraphs and returns ``replay() -> device f32[2]``
+        (loss, top-1), under DPCEngine.capture_train_step's contract: cached by (static input buffer, exchange, carve-out, side_off,
+        refill identity, baked host scalars -- lr, wd, both dropouts and seeds, the Adam segment table); a replay raises once one of
+        the baked values changed; every replay is one optimizer step; the graphs are parked, never destroyed.  The labels are read
+        from ``self.target`` as they stand: drawn inside the graph by ``refill=lambda: eng.fill_synthetic(seed)``, or set eagerly
+        before each replay (set_labels).  block=None: the step starts from the stem's operand (load_recipe / fill_synthetic).
+
+        Where the backward stops (grad_wanted(): the optimizer's groups, no_grad_params) is decided HERE and is part of the key.
+        One graph without an exchange.  With the two-bucket exchange and a full backward: graph A (forward, backward down to layer2)
+        -> allreduce.start(tail) -> graph B (layer1 + stem) -> allreduce.finish(head) -> graph C (Adam), cut where DPCEngine cuts.
+        With a truncated backward (a frozen backbone) there is nothing between the two exchange points, so the capture is cut ONCE:
+        graph A (forward, head / ConvGRU backward) -> allreduce.start(tail) -> allreduce.finish(empty first bucket), as the eager
+        step does -> graph B (Adam).  No empty hipGraph is created or replayed."""
+        buf = self.x_s2d if block is None else block
+        need_backbone = self.grad_wanted()[0]
+        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
+               id(refill) if refill is not None else None, tuple(sorted(self.no_grad_params))) + self._baked_scalars()
+        two_bucket = allreduce is not None and hasattr(allreduce, "start")
+        split = self.grad_split if need_backbone else 0   # the first bucket of the exchange: empty when the backward was truncated
+        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:split], self.flat_g, self.result
+
+        def warm():
+            for _ in range(warmup):
+                self.train_step(block, None, allreduce=allreduce)
+
+        def body(cut):
+            self.forward(block, None, train=True)
+            if two_bucket and not need_backbone:   # backward() hands the tail over and returns: one cut serves both exchange points
+                self.backward(on_tail_ready=lambda _tail: None)
+                cut()
+            else:
+                self.backward(on_tail_ready=cut if two_bucket else None)
+                if allreduce is not None:
+                    cut()
+            host_steps = self._step_count
+            self.adam_step()
+            self._step_count = host_steps  # capture executes nothing
+
+        def run(eng, graphs):
+            graphs[0].replay()
+            if two_bucket:
+                allreduce.start(tail)
+                if need_backbone:
+                    graphs[1].replay()
+                allreduce.finish(head)
+                graphs[-1].replay()
+            elif allreduce is not None:
+                allreduce(whole)
+                graphs[1].replay()
+            eng._step_count += 1
+            eng.packed_for_step = -1
+            return result
+
+        return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
+                             refill, block=buf)
+
+    def capture_eval_step(self, refill=None):
+        """Captures one evaluation step on the stem's operand and the labels as they stand -- `refill`, then forward(None, None,
+        train=False) -- into one hipGraph and returns ``replay() -> device f32[2]``.  The weight repack is inside the graph, so a replay
+        evaluates the weights and running buffers of now.  Same rules as capture_train_step.  No eager warm-up: run one eager
+        eval-mode forward first (it allocates its ReLU masks on first use)."""
+        key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
+        result = self.result
+
+        def warm():
+            if self._pack_table is None:
+                self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
+
+        def body(cut):
+            self.forward(None, None, train=False)
+
+        def run(eng, graphs):
+            graphs[0].replay()
+            return result
+
+        return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
 
     # ---- the video-level test of eval/test.py:303-343 (csrc/lc_test.hip): per-video state, run totals and the confusion matrix on the device
     def test_reset(self):
@@ -235,14 +336,16 @@ class LCEngine(BackboneEngine):
         self.test_totals, self.test_confusion = z(4, dt=torch.float64), z(NC, NC, dt=torch.int64)
         self.test_label = torch.zeros(self.B, dtype=torch.int64)
 
-    def test_video(self, frames_u8, label: int, starts, clip: dict, ds: int = 3, vlen: Optional[int] = None):
+    def test_video(self, frames_u8, label: int, starts, clip: dict, ds: int = 3, vlen: Optional[int] = None, graph: bool = False):
         """one video of the test protocol: frames_u8 uint8 [vlen, H0, W0, 3] (host array or tensor; uploaded ONCE), its class label,
         the window start frames (data.lc_test_windows) and the test recipe's draw (data.draw_lc(..., 'test')).  Per chunk of B windows:
         gather into the stem's operand (dpc_video_windows_to_input) -> eval-mode forward -> dpc_lc_test_accumulate with the chunk's
         valid count; the last chunk is padded by repeating its last window (finite rows; eval-mode BatchNorm uses running statistics,
         so rows do not see each other) and its padding rows are never summed.  Then dpc_lc_test_finish.  Nothing crosses to the
         host: ``test_res`` (loss, top-1, top-5, pred), ``test_prob`` (mean probability) hold this video, ``test_totals`` /
-        ``test_confusion`` the run (``test_reset`` starts one)."""
+        ``test_confusion`` the run (``test_reset`` starts one).  graph=True: the per-chunk forward is a replay of capture_eval_step()
+        (the label is set once per video; the gather and the accumulation, whose arguments differ per chunk, stay eager; the engine's
+        first eval-mode forward is eager, as capture_eval_step asks)."""
         from .data import video_windows_to_input
         if not hasattr(self, "test_totals"):
             self.test_reset()
@@ -257,12 +360,20 @@ class LCEngine(BackboneEngine):
         vlen = video.shape[0] if vlen is None else int(vlen)
         B = self.B
         self.test_label.fill_(label)
+        if graph:
+            self.check_graph_capture()
+            self.set_labels(self.test_label)
         for i in range(0, len(starts), B):
             st = starts[i:i + B]
             n_valid = len(st)
             st = st + [st[-1]] * (B - n_valid)
             video_windows_to_input(self.lib, video, vlen, st, clip, self.N, self.SL, ds, self.size, None, self.x_s2d)
-            self.forward(None, self.test_label, train=False)
+            if not graph:
+                self.forward(None, self.test_label, train=False)
+            elif not self._eval_ran:
+                self.forward(None, None, train=False)
+            else:
+                self.capture_eval_step()()
             self.call("dpc_lc_test_accumulate", self.logits, B, n_valid, self.num_class, self.num_class, self.test_psum, self.test_lsum,
                       self.test_count)
         self.call("dpc_lc_test_finish", self.test_psum, self.test_lsum, self.test_count, self.num_class, label, self.test_prob, self.test_res,

@@ -87,6 +87,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--val_labels', default='', type=str, help='labels of --val_frames')
     parser.add_argument('--val_lengths', default='', type=str, help='lengths of --val_frames')
     parser.add_argument('--crop', default=224, type=int, help='side of RandomSizedCrop / CenterCrop in the recipes (eval/test.py:122,162,170)')
+    parser.add_argument('--graph', action='store_true', help='after two eager train steps and one eager validation step, replay ONE captured '
+                        'hipGraph per kind of step (HIP device only; a changed learning rate captures a new step).  Synthetic input: batch '
+                        'and labels are drawn on the device inside the graph (LCEngine.fill_synthetic) -- NOT the batches of a run without '
+                        '--graph; with --frames the batches, parameters and log lines are those of the run without it.  With --test '
+                        '--frames: the per-chunk forward of the video-level test is a replayed graph, same totals')
     return parser
 
 
@@ -145,6 +150,8 @@ def _worker(rank: int, world: int, args, port: int):
     widths = getattr(args, '_widths', None) or LAYER_WIDTH
     eng = LCEngine(args.net, args.img_dim, args.num_seq, args.seq_len, per_gpu, dev, cdt, widths, lib=sim, lr=args.lr, wd=args.wd,
                    dropout=args.dropout, num_class=args.num_class, seed=666 + rank)  # model_3d_lc.py:16 seeds 666
+    if args.graph:
+        eng.check_graph_capture()   # before the first step: --graph never falls back to kernel-by-kernel launches
     init = LC(args.img_dim, args.num_seq, args.seq_len, args.net, args.dropout, args.num_class, widths=widths, seed=0)
     eng.load_params({k: v.detach() for k, v in init.state_dict().items()})
     log = print if rank == 0 else (lambda *a, **k: None)
@@ -163,8 +170,14 @@ def _worker(rank: int, world: int, args, port: int):
         groups = [([k for k in eng.offsets if k.startswith(('final_bn.', 'final_fc.'))], base_lr)]
         log('=> train only final_bn / final_fc on a frozen backbone + ConvGRU (batch statistics, running buffers updated)')
 
+    # --graph: per run, the first `warm[train]` steps of each kind run eagerly, then one captured step per kind is replayed.  lr / wd / the
+    # segment table are baked into a capture: set_lr drops the entry's handle, and the next step asks the engine again -- the replay that
+    # exists when nothing changed, a new capture (the old one stays parked) when the schedule passed a milestone
+    warm, captured = {True: 2, False: 1}, {True: None, False: None}
+
     def set_lr(mult, saved=None):
         """the schedule scales every group; saved: the groups' lrs of a resumed checkpoint"""
+        captured[True] = captured[False] = None
         eng.lr = base_lr * mult
         if groups is not None:
             lrs = saved if saved is not None else [lr * mult for _, lr in groups]
@@ -227,7 +240,7 @@ def _worker(rank: int, world: int, args, port: int):
             t0 = time.time()
             eng.test_reset()
             for _, frames, label, starts, clip in src_test.videos():
-                eng.test_video(frames, label, starts, clip, ds=args.ds)
+                eng.test_video(frames, label, starts, clip, ds=args.ds, graph=args.graph)
             loss_sum, top1, top5, n_vid = eng.test_totals.cpu().tolist()   # the ONE readback of the run (+ the confusion matrix below)
             confusion = eng.test_confusion.cpu()
             n = max(n_vid, 1.0)
@@ -274,34 +287,62 @@ def _worker(rank: int, world: int, args, port: int):
         log('Loss {:.4f}\t Acc top1: {:.4f} Acc top5: {:.4f} \t'.format(loss_sum / n, top1 / n, top5 / n))
         log('(test checkpoint epoch {})'.format(num_epoch))
     else:
+        # --graph, synthetic input: `refill` draws batch and labels on the device in front of the step (inside the graph once captured);
+        # --frames: load_recipe and set_labels fill operand and labels eagerly before each step and the graph starts from them
+        refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
+
+        def step(train: bool, feed):
+            """one train / validation step, eager or replayed; returns (device f32[2], replayed)"""
+            x = y = None
+            if feed is not None:
+                frames, starts, clips, y = next(feed)
+                eng.load_recipe(frames, starts, clips, ds=args.ds)   # fills the stem's operand; no f32 video in between
+            elif not args.graph:
+                x, y = batch()
+            if args.graph and warm[train] == 0:
+                if y is not None:
+                    eng.set_labels(y)
+                if captured[train] is None:
+                    captured[train] = (eng.capture_train_step(None, allreduce=allreduce, warmup=0, refill=refill) if train
+                                       else eng.capture_eval_step(refill))
+                return captured[train], True
+            if args.graph:   # eager warm-up step
+                warm[train] -= 1
+                if refill is not None:
+                    refill()
+            if train:
+                return eng.train_step(x, y, allreduce=allreduce), False
+            eng.forward(x, y, train=False)
+            return eng.result, False
+
         for epoch in range(args.start_epoch, args.epochs):
             n_train = len(src_train) if src_train is not None else args.synthetic
             feed = src_train.epoch(dev) if src_train is not None else None
+            replayed, ev0, ev1 = 0, None, None
             for idx in range(n_train):  # train(): eval/test.py:218-271
-                if feed is not None:
-                    frames, starts, clips, y = next(feed)
-                    eng.load_recipe(frames, starts, clips, ds=args.ds)   # fills the stem's operand; no f32 video in between
-                    x = None
-                else:
-                    x, y = batch()
-                res = eng.train_step(x, y, allreduce=allreduce)
+                res, replay = step(True, feed)
+                if replay:
+                    if ev0 is None:
+                        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        ev0.record()
+                    res = res()
+                    ev1.record()
+                    replayed += 1
                 if idx % args.print_freq == 0:
                     loss, acc = reduce(res)
                     log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr),
                         flush=True)
                     iteration += 1  # advanced on logged steps only, as the reference does (eval/test.py:262-270)
+            if replayed:   # device time from the first replayed train step of the epoch to the end of its last one
+                ev1.synchronize()
+                ms = ev0.elapsed_time(ev1) / replayed
+                log('Graph replay: {0} steps, {1:.3f} ms/step, {2:.1f} clips/s'.format(replayed, ms, args.batch_size * 1e3 / ms), flush=True)
             vl = va = 0.0
             n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
             feed = src_val.epoch(dev) if src_val is not None else None
             for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
-                if feed is not None:
-                    frames, starts, clips, y = next(feed)
-                    eng.load_recipe(frames, starts, clips, ds=args.ds)
-                    x = None
-                else:
-                    x, y = batch()
-                eng.forward(x, y, train=False)
-                loss, acc = reduce(eng.result)
+                res, replay = step(False, feed)
+                loss, acc = reduce(res() if replay else res)
                 vl += loss
                 va += acc
             nv = max(n_val, 1)

@@ -200,6 +200,12 @@ int dpc_pack_input_s2d(const float* block, void* out, int32_t dtype_out, int32_t
  *   dpc_counter_advance in front of it gives every replay of a captured step a new batch. */
 int dpc_synthetic_input(float* block, void* out, int32_t dtype_out, int32_t BN, int32_t T, int32_t H, int32_t W, uint64_t seed,
                         const int32_t* draw_dev, dpc_stream_t stream);
+/* dpc_synthetic_labels: the class labels of a synthetic batch drawn on the device into target [B] int64 (csrc/labels.hip).
+ *   (w0..w3) = Philox4x32-10(counter (b >> 2, draw_dev[0], 3 = DPC_PHILOX_STREAM_LABEL, 0), key (lo(seed), hi(seed)));
+ *   label[b] = ((uint64)w_(b & 3) * num_class) >> 32, in [0, num_class).  The draw counter is read on the device, never written,
+ *   exactly like dpc_synthetic_input: with the same seed and counter the labels belong to that call's batch.
+ *   DPC_ERR_ARG for null pointers, B <= 0 or num_class <= 0. */
+int dpc_synthetic_labels(int64_t* target, int32_t B, int32_t num_class, uint64_t seed, const int32_t* draw_dev, dpc_stream_t stream);
 int dpc_pack_stem_weight(const float* w, void* out, int32_t dtype_out, int32_t Co, dpc_stream_t stream);
 int dpc_unpack_stem_wgrad(const float* part, int32_t nsplit, float* dw, int32_t Co, dpc_stream_t stream);
 
