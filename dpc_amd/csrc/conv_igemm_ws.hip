@@ -25,7 +25,6 @@
 // The epilogue stages each wave's 64 x 128 block through the LDS stage that was read last (free until
 // the next chunk barrier) in two wave-private 32-row passes -- no workgroup barrier inside.
 #include "conv_common.h"
-#include <stdlib.h>
 
 struct WsParams {
     GatherGeom g;
@@ -58,7 +57,7 @@ struct WsParams {
 #define WS_DBG(bit) 0
 #endif
 
-#include "ws_frag.h"
+#include "ws_common.h"
 
 template <bool HAS_ADD, bool PAR = false>
 __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
@@ -67,7 +66,6 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
     constexpr int BM = 256, BN = 128, BKE = 64;
     constexpr int STAGE = (BM + BN) * 128;  // 48 KB
     constexpr int NST = 3;
-    constexpr int EPO = 8, UPR = BN / EPO;  // 16 output units per row
     // Round 3 claimed all 160 KB here "so that no LDS-using workgroup can sit beside this one": beside an 8 KB-LDS kernel of another
     // stream 38 of 15 000 launches came back with one wave's 64 x 128 block wrong.  Round 4 found the mechanism (WS_RETIRE_TAIL_READS
     // below, scripts/asm_hazard_lint.py): it was a register hazard of the end-of-tile fragment reads, not the ring's ordering, and a
@@ -76,13 +74,8 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NST * STAGE];
 
     const GatherGeom& g = p.g;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-#ifdef DPC_SIMT_EMU
-    const int wv = tid >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+    const WsWave w = ws_wave_id();
+    const int tid = w.tid, lane = w.lane, wv = w.wv;
     const int n_tile = blockIdx.x / p.gm;
     const int m_prog = blockIdx.x % p.gm;
     const int nkc = g.Kp / BKE;
@@ -317,17 +310,12 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
     const ldsa_t lds0 = ldsa(lds);
     const int fa0 = lds_unit_off(wv * 64 + l31, lhi);
     const int fb0 = BM * 128 + lds_unit_off(l31, lhi);
-    // epilogue lane constants: a pass stages 32 rows x 128 columns (8 KB) per wave
-    const int cu = lane & 15, er = lane >> 4;  // output unit column, first row of the lane inside a pass (rows er + 4*it)
-    const int col0 = n_tile * BN + cu * EPO;
-    float s1[EPO], s2[EPO];
-    DPC_UNROLL
-    for (int e = 0; e < EPO; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    const int cu = lane & 15, er = lane >> 4;   // output unit of the lane, its first row inside an epilogue pass (rows er + 4*it)
+    const int col0 = n_tile * BN + cu * WS_EPO;  // first column of the lane's output unit
+    float s1[WS_EPO] = {}, s2[WS_EPO] = {};
 
     int gc = 0;
-#ifndef DPC_SIMT_EMU
-    __builtin_amdgcn_s_setprio(3);   // the compute waves win the SIMD's issue arbitration against their loader partner (-1..2 %)
-#endif
+    ws_compute_prio();
     for (int t = 0; wv < 4 && t < my_tiles; ++t) {
         const int mt = m_prog + t * p.gm;
         ParCls ck = {};
@@ -335,13 +323,7 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
         int kc_lo, kc_hi;
         tile_chunks(mt, kc_lo, kc_hi);
         const int nkc_t = kc_hi - kc_lo;
-        f32x16 acc[2][4];
-        DPC_UNROLL
-        for (int i = 0; i < 2; ++i)
-            DPC_UNROLL
-            for (int j = 0; j < 4; ++j)
-                DPC_UNROLL
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        f32x16 acc[2][4] = {};
         // The chunk loop is software-pipelined ACROSS the chunk barrier: the barrier that publishes chunk
         // gc+1 sits between MFMA steps 2 and 3 of chunk gc (all LDS reads of chunk gc are complete by then, so
         // it is also the "stage gc may be refilled" point), and the first fragments of chunk gc+1 are read
@@ -350,7 +332,9 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
         // rate measured) or, given two sets, waits lgkmcnt(0) -- i.e. also for the reads it has just issued.
         // Barrier sequence per tile, identical to the loaders': B(c0) B(c1) ... B(c_last) B("tile fully read").
         // residual addend (input-gradient of a block's first conv): requested ahead of the epilogue -- issued inside
-        // it, 8 x 16 B per lane in flight made the extra tensor read cost +150 us on layer2
+        // it, 8 x 16 B per lane in flight made the extra tensor read cost +150 us on layer2.
+        // NOT shared with igemm_wsp_kernel's copy: moved into a helper, in any form, the pointer select below is canonicalised
+        // before it is inlined and igemm_ws_kernel<true> comes out with 20 global loads for 16 (four of them in both arms of a branch)
         u32x4 av0[8], av1[8];
         auto fetch_addend = [&](int i, u32x4 (&dst)[8]) {
             DPC_UNROLL
@@ -382,7 +366,8 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
                 pa = lds0 + (gc % NST) * STAGE + fa0;
                 pb = lds0 + (gc % NST) * STAGE + fb0;
                 // after the tile's last chunk these reads fetch nothing useful (the next tile re-reads after ITS first barrier):
-                // unconditional, so that the MFMAs stay out of a branch (accumulators joined after a branch are copied and spill)
+                // unconditional, so that the MFMAs stay out of a branch -- accumulators that flow through both arms of a branch are
+                // copied at the join (hundreds of spilled registers)
                 step_il<true, 4096>(acc, f1, f0, pa, pb);
             }
             WS_RETIRE_TAIL_READS(f0);   // the reads past the tile's last chunk land before their registers are handed on
@@ -396,74 +381,26 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
         unsigned char* mine = lds + stage_last * STAGE + wv * WS_STG_WAVE;   // 34 KB of the 48 KB stage every wave has finished reading
         DPC_UNROLL
         for (int i = 0; i < 2; ++i) {
-            stage_block(mine, acc[i], l31, lhi);
-            wave_lds_fence();  // wave-private region: LDS operations of one wave complete in order, no workgroup barrier
+            ws_stage_pass(mine, acc[i], l31, lhi);
             if (HAS_ADD && i == 0) fetch_addend(1, av1);  // the first pass's accumulators are dead: room for the second pass's addend
             u32x4 ov[8];
             DPC_UNROLL
-            for (int it = 0; it < 8; ++it) {
-                const int row_l = er + 4 * it;
-                ov[it] = *(const u32x4*)(mine + row_l * WS_STG_ROW + cu * EPO * 2);
-            }
-            wave_lds_fence();  // the second pass overwrites what this one has just read
+            for (int it = 0; it < 8; ++it) ov[it] = ws_staged_unit(mine, er + 4 * it, cu * WS_EPO);
+            wave_lds_fence();  // the next pass overwrites what this one has just read
             DPC_UNROLL
             for (int it = 0; it < 8; ++it) {
                 const int row = PAR ? par_row(ck, wv * 64 + i * 32 + er + 4 * it) : tile_row(mt, wv * 64 + i * 32 + er + 4 * it);
                 if (row < g.M && col0 < p.Ncol) {
                     u32x4 o = ov[it];
-                    if (HAS_ADD) {
-                        const u32x4 a = i == 0 ? av0[it] : av1[it];
-                        float sv[EPO];
-                        DPC_UNROLL
-                        for (int e = 0; e < EPO; ++e) sv[e] = unit_get<TO>(o, e) + unit_get<TO>(a, e);
-                        o = unit_pack<TO>(sv);
-                    }
+                    if (HAS_ADD) o = ws_unit_add(o, i == 0 ? av0[it] : av1[it]);
                     *(u32x4*)((char*)p.out + ((long long)row * p.ldo + col0) * 2) = o;
-                    if (!HAS_ADD) {  // batch-norm partial sums belong to forward convs; those have no residual addend
-                        DPC_UNROLL
-                        for (int e = 0; e < EPO; ++e) {
-                            const float v = unit_get<TO>(o, e);
-                            s1[e] += v;
-                            s2[e] += v * v;
-                        }
-                    }
+                    if (!HAS_ADD) ws_unit_sums(o, s1, s2);
                 }
             }
         }
     }
 
-    if (!HAS_ADD && p.stats) {
-        // 16 lanes x 4 compute waves hold partial sums of the same 8 columns: fold the 4 row-lanes of a wave
-        // by shuffles, then the 4 waves through LDS (the loader waves only keep the barriers company).
-        DPC_UNROLL
-        for (int e = 0; e < EPO; ++e) {
-            s1[e] += __shfl_xor(s1[e], 16); s1[e] += __shfl_xor(s1[e], 32);
-            s2[e] += __shfl_xor(s2[e], 16); s2[e] += __shfl_xor(s2[e], 32);
-        }
-        float* red = (float*)lds;  // [4 waves][2][128]
-        __syncthreads();
-        if (wv < 4 && lane < 16) {
-            DPC_UNROLL
-            for (int e = 0; e < EPO; ++e) {
-                red[(wv * 2 + 0) * BN + cu * EPO + e] = s1[e];
-                red[(wv * 2 + 1) * BN + cu * EPO + e] = s2[e];
-            }
-        }
-        __syncthreads();
-        if (tid < BN) {
-            const int col = n_tile * BN + tid;
-            if (col < p.Ncol) {
-                float a = 0.f, b = 0.f;
-                DPC_UNROLL
-                for (int w = 0; w < 4; ++w) {
-                    a += red[(w * 2 + 0) * BN + tid];
-                    b += red[(w * 2 + 1) * BN + tid];
-                }
-                p.stats[((long long)m_prog * 2 + 0) * p.Ncol + col] = a;
-                p.stats[((long long)m_prog * 2 + 1) * p.Ncol + col] = b;
-            }
-        }
-    }
+    if (!HAS_ADD && p.stats) ws_stats_tail(lds, s1, s2, p.stats, p.Ncol, m_prog, n_tile, tid, wv);
 }
 
 
@@ -495,24 +432,14 @@ __global__ __launch_bounds__(512, 2) void igemm_ws_kernel(WsParams p) {
 template <bool HAS_ADD>
 __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
     typedef bf16_t TO;
-    constexpr int BM = 256, BN = 128;
-    constexpr int PWD = 18, NPP = PWD * PWD, NPIECE = (NPP + 7) / 8, PATCH = NPIECE * 1024;  // 324 positions, 41 pieces
-    constexpr int BST = BN * 128, NSB = 4;
-    constexpr int EPO = 8;
-    constexpr int MAXP = (NPIECE + 3) / 4;  // patch pieces per loader wave
-    static_assert(4 * WS_STG_WAVE <= PATCH, "epilogue staging fits a patch buffer");
-    static_assert(2 * PATCH + NSB * BST <= 160 * 1024, "patches + ring fit the CU's LDS");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * PATCH + NSB * BST];
+    constexpr int BM = WS_BM, BN = WS_BN;
+    constexpr int PWD = WSP_PWD, PATCH = WSP_PATCH, BST = WSP_BST, NSB = WSP_NSB, EPO = WS_EPO;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[WSP_LDS];
     unsigned char* const bring = lds + 2 * PATCH;
 
     const GatherGeom& g = p.g;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-#ifdef DPC_SIMT_EMU
-    const int wv = tid >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+    const WsWave w = ws_wave_id();
+    const int tid = w.tid, lane = w.lane, wv = w.wv;
     const int n_tile = blockIdx.x / p.gm;
     const int m_prog = blockIdx.x % p.gm;
     const int G = g.Ci >> 6;       // channel groups of 64
@@ -525,7 +452,6 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
         // ------------------------------------------------------------------ loader waves
         const int lw = wv - 4;
         const int rl = lane >> 3;
-        const BufRsrc rs_a = make_buf_rsrc(p.src, p.src_bytes);
         const BufRsrc rs_b = make_buf_rsrc(p.wgt, p.wgt_bytes);
         const int ub = (lane & 7) ^ lds_swz1(8 * lw + rl);   // weights: same stage image as igemm_ws_kernel
         unsigned wrow[4];
@@ -534,109 +460,39 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
             const int n = n_tile * BN + 8 * (lw + 4 * i) + rl;
             wrow[i] = n < p.Ncol ? (unsigned)(n * p.ldw + ub * 8) * 2u : DPC_BUF_OOB;
         }
-        // patch piece j = lw + 4i holds patch positions 8j .. 8j+7; a lane fetches unit (slot ^ swizzle(patch column)) of its
-        // position.  The offsets are relative to the plane: the same for every tile.
-        unsigned poff[MAXP];
-        DPC_UNROLL
-        for (int i = 0; i < MAXP; ++i) {
-            const int pp = 8 * (lw + 4 * i) + rl;
-            const int pr = pp / PWD, pc = pp - pr * PWD;
-            const bool ok = pp < NPP && pr >= 1 && pr <= 16 && pc >= 1 && pc <= 16;
-            const int up = (lane & 7) ^ ((pc >> 1) & 7);
-            poff[i] = ok ? (unsigned)((((pr - 1) * 16 + (pc - 1)) * g.src_ld + up * 8) * 2) : DPC_BUF_OOB;
-        }
-        const int n_mine = (NPIECE - lw + 3) / 4;
-        int issued = 0;               // operations issued in the current slot
-        auto issue_patch = [&](int gg, int i0, int i1) {   // pieces [i0, i1) of this wave, of global group gg
-            const int tl = gg / G, grp = gg - tl * G;
-            const int mt = WS_DBG(512) ? m_prog & 7 : m_prog + tl * p.gm;
-            const unsigned soff = (unsigned)((mt * BM * g.src_ld + grp * 64) * 2);
-            unsigned char* dst = lds + (gg & 1) * PATCH;
-            DPC_UNROLL
-            for (int i = 0; i < MAXP; ++i)
-                if (i >= i0 && i < i1 && i < n_mine && !WS_DBG(4 | 128)) {
-                    glds16_buf(rs_a, poff[i], soff, dst + (lw + 4 * i) * 1024, lane);
-                    ++issued;
-                }
-        };
-        auto issue_b = [&](int gc) {
+        auto issue_b = [&](int gc) -> int {
             const int gg = gc / 9, tap = gc - gg * 9;
             const int grp = gg % G;
             const int kd = tap * g.Ci + grp * 64;
             unsigned char* st = bring + (gc % NSB) * BST;
-            if (WS_DBG(4 | 256)) return;
+            if (WS_DBG(4 | 256)) return 0;
             DPC_UNROLL
             for (int i = 0; i < 4; ++i) glds16_buf(rs_b, wrow[i], (unsigned)kd * 2u, st + (lw + 4 * i) * 1024, lane);
-            issued += 4;
+            return 4;
         };
-        // A slot = what is issued between two chunk barriers: patch pieces first, the weights of chunk c+3 last.  The weights of
-        // chunk c are the last operations of slot c-3, so "at most (slot c-2) + (slot c-1) operations outstanding" means landed.
-        // The prologue counts as slots -3 (patch of group 0 + chunk 0), -2 (chunk 1), -1 (chunk 2).
-        if (total > 0) {
-            issue_patch(0, 0, MAXP);
-            issue_b(0);
-        }
-        issued = 0;
-        if (total > 1) issue_b(1);
-        int o2 = issued;
-        issued = 0;
-        if (total > 2) issue_b(2);
-        int o1 = issued;
-        for (int gc = 0; gc < total; ++gc) {
-            wait_vmcnt_upto(o1 + o2);
-            if (!WS_DBG(32)) ws_barrier();  // chunk gc (and, at a group's first chunk, its patch) is published; every reader is done with chunk gc-1
-            const int gg = gc / 9, q = gc - gg * 9;
-            issued = 0;
-            if (q < (MAXP + 1) / 2 && (gg + 1) * 9 < total) issue_patch(gg + 1, 2 * q, 2 * q + 2);
-            if (gc + 3 < total) issue_b(gc + 3);
-            o2 = o1;
-            o1 = issued;
-            if (q == 8 && (gg + 1) % G == 0) if (!WS_DBG(32)) ws_barrier();  // matches the compute waves' "tile fully read" barrier
-        }
+        // nine chunks (taps) per group; the next group's patch goes out two pieces per slot
+        const WsPatchPlan pl = {.m_prog = m_prog, .mstride = p.gm, .G = G, .cpg = 9, .pslots = (WSP_MAXP + 1) / 2, .total = total};
+        ws_patch_loader(lds, p.src, p.src_bytes, g.src_ld, lane, lw, pl, WS_DBG(~0), issue_b);
     }
 
     // ---------------------------------------------------------------------- compute waves
     const int l31 = lane & 31, lhi = lane >> 5;
-    // A-fragment addresses.  Row r of the tile is pixel (r >> 4, r & 15); for tap (kh, kw) it reads patch position
-    // (r>>4 + dh) * 18 + (r&15) + dw with (dh, dw) = (kh, kw) forward, (2-kh, 2-kw) input-gradient; the second fragment (+32 rows =
-    // +2 image rows) is 36 positions = 4608 bytes further in the same patch column.  The 16-byte slots of a position are
-    // XOR-swizzled by (patch column >> 1) & 7: a ds_read_b128 lane group is 8 + 8 lanes of two image rows
-    // (MI355X_MICROARCH.md, LDS) whose columns c+{0..3,12..15} and c+{4..11} then cover 16 distinct (column parity, slot) pairs =
-    // all 64 banks; swizzling by the position (row pitch 18) does not.  Everything that depends on the lane is tabulated per kw
-    // (12 registers); the kh / patch-buffer part is a scalar added per chunk.
-    // slot bits = ((2kk + lhi) ^ p7) << 4 = ((lhi ^ p7) << 4) ^ (kk << 5), and every base below is a multiple of 128: the address
-    // of step kk is (chunk base + va[kw]) ^ (kk << 5) -- one register per kw instead of a 12-entry table.
+    // A-fragment addresses (ws_patch_va): tap (kh, kw) shifts a row's patch position by (dh, dw) = (kh, kw) forward, (2-kh, 2-kw)
+    // input-gradient; one register per kw
     int va[3];
-    {
-        const int pos0 = ((wv * 64 + l31) >> 4) * PWD + (l31 & 15);
-        DPC_UNROLL
-        for (int kw = 0; kw < 3; ++kw) {
-            const int dw = g.mode == 0 ? kw : 2 - kw;
-            const int p7 = (((l31 & 15) + dw) >> 1) & 7;
-            va[kw] = (pos0 + dw) * 128 + ((lhi ^ p7) << 4);
-        }
-    }
+    const int dws[3] = {g.mode == 0 ? 0 : 2, 1, g.mode == 0 ? 2 : 0};
+    ws_patch_va(va, dws, wv, l31, lhi);
     const ldsa_t lds0 = ldsa(lds);
     const int vb = lds_unit_off(l31, lhi);   // B fragment of step 0; step kk: ^ (kk << 5) (stage bases are multiples of 16 KB)
-    const int cu = lane & 15, er = lane >> 4;
-    const int col0 = n_tile * BN + cu * EPO;
-    float s1[EPO], s2[EPO];
-    DPC_UNROLL
-    for (int e = 0; e < EPO; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
+    const int er = lane >> 4;
+    const int col0 = n_tile * BN + (lane & 15) * EPO;
+    float s1[EPO] = {}, s2[EPO] = {};
 
     int gc = 0;
-#ifndef DPC_SIMT_EMU
-    __builtin_amdgcn_s_setprio(3);   // the compute waves win the SIMD's issue arbitration against their loader partner (-1..2 %)
-#endif
+    ws_compute_prio();
     for (int t = 0; wv < 4 && t < my_tiles; ++t) {
         const int mt = m_prog + t * p.gm;
-        f32x16 acc[2][4];
-        DPC_UNROLL
-        for (int i = 0; i < 2; ++i)
-            DPC_UNROLL
-            for (int j = 0; j < 4; ++j)
-                DPC_UNROLL
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        f32x16 acc[2][4] = {};
         u32x4 av0[8], av1[8];
         auto fetch_addend = [&](int i, u32x4 (&dst)[8]) {
             DPC_UNROLL
@@ -644,10 +500,7 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
                 const int row = mt * BM + wv * 64 + i * 32 + er + 4 * it;
                 const bool ok = row < g.M && col0 < p.Ncol;
                 const char* a = (const char*)p.addend + ((long long)row * p.ldo + col0) * 2;
-                // rows outside the tensor read its unit 0 (never used: their outputs are not stored).  Not the zero page: a select between
-                // a kernel-argument pointer and a device constant is a GENERIC pointer, its flat loads count on lgkmcnt as well and hipcc
-                // waits lgkmcnt(0) for them -- behind the hand-issued fragment reads of the chunk (scripts/asm_drain_lint.py)
-                dst[it] = *(const u32x4*)(ok ? a : (const char*)p.addend);
+                dst[it] = *(const u32x4*)(ok ? a : (const char*)p.addend);   // unit 0, not the zero page: see igemm_ws_kernel
             }
         };
         // Chunk loop: (channel group, kh) outer, kw unrolled (its address table is then a compile-time choice).  Four steps per
@@ -681,10 +534,7 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
                     if (KW == 2) a_row = a_row_n;
                     pa = a_row + va[(KW + 1) % 3];
                     pb = b_st + vb;
-                    // after the tile's last chunk these reads fetch nothing useful (the next tile re-reads after ITS first barrier):
-                    // keeping them unconditional keeps the MFMAs out of a branch -- accumulators that flow through both arms
-                    // of a branch are copied at the join (hundreds of spilled registers)
-                    step_il<true, 4608>(acc, f1, f0, pa, pb);
+                    step_il<true, 4608>(acc, f1, f0, pa, pb);   // unconditional, as in igemm_ws_kernel
                 });
             }
             WS_RETIRE_TAIL_READS(f0);   // see the macro: reads past the tile's last chunk land before their registers are handed on
@@ -698,72 +548,26 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
         }
         DPC_UNROLL
         for (int i = 0; i < 2; ++i) {
-            stage_block(mine, acc[i], l31, lhi);
-            wave_lds_fence();
+            ws_stage_pass(mine, acc[i], l31, lhi);
             if (HAS_ADD && i == 0) fetch_addend(1, av1);
             u32x4 ov[8];
             DPC_UNROLL
-            for (int it = 0; it < 8; ++it) {
-                const int row_l = er + 4 * it;
-                ov[it] = *(const u32x4*)(mine + row_l * WS_STG_ROW + cu * EPO * 2);
-            }
-            wave_lds_fence();
+            for (int it = 0; it < 8; ++it) ov[it] = ws_staged_unit(mine, er + 4 * it, (lane & 15) * WS_EPO);
+            wave_lds_fence();  // the next pass overwrites what this one has just read
             DPC_UNROLL
             for (int it = 0; it < 8; ++it) {
                 const int row = mt * BM + wv * 64 + i * 32 + er + 4 * it;
                 if (row < g.M && col0 < p.Ncol && !WS_DBG(1)) {
                     u32x4 o = ov[it];
-                    if (HAS_ADD) {
-                        const u32x4 a = i == 0 ? av0[it] : av1[it];
-                        float sv[EPO];
-                        DPC_UNROLL
-                        for (int e = 0; e < EPO; ++e) sv[e] = unit_get<TO>(o, e) + unit_get<TO>(a, e);
-                        o = unit_pack<TO>(sv);
-                    }
+                    if (HAS_ADD) o = ws_unit_add(o, i == 0 ? av0[it] : av1[it]);
                     *(u32x4*)((char*)p.out + ((long long)row * p.ldo + col0) * 2) = o;
-                    if (!HAS_ADD) {
-                        DPC_UNROLL
-                        for (int e = 0; e < EPO; ++e) {
-                            const float v = unit_get<TO>(o, e);
-                            s1[e] += v;
-                            s2[e] += v * v;
-                        }
-                    }
+                    if (!HAS_ADD) ws_unit_sums(o, s1, s2);
                 }
             }
         }
     }
 
-    if (!HAS_ADD && p.stats) {
-        DPC_UNROLL
-        for (int e = 0; e < EPO; ++e) {
-            s1[e] += __shfl_xor(s1[e], 16); s1[e] += __shfl_xor(s1[e], 32);
-            s2[e] += __shfl_xor(s2[e], 16); s2[e] += __shfl_xor(s2[e], 32);
-        }
-        float* red = (float*)lds;  // [4 waves][2][128]
-        __syncthreads();
-        if (wv < 4 && lane < 16) {
-            DPC_UNROLL
-            for (int e = 0; e < EPO; ++e) {
-                red[(wv * 2 + 0) * BN + cu * EPO + e] = s1[e];
-                red[(wv * 2 + 1) * BN + cu * EPO + e] = s2[e];
-            }
-        }
-        __syncthreads();
-        if (tid < BN) {
-            const int col = n_tile * BN + tid;
-            if (col < p.Ncol) {
-                float a = 0.f, b = 0.f;
-                DPC_UNROLL
-                for (int w = 0; w < 4; ++w) {
-                    a += red[(w * 2 + 0) * BN + tid];
-                    b += red[(w * 2 + 1) * BN + tid];
-                }
-                p.stats[((long long)m_prog * 2 + 0) * p.Ncol + col] = a;
-                p.stats[((long long)m_prog * 2 + 1) * p.Ncol + col] = b;
-            }
-        }
-    }
+    if (!HAS_ADD && p.stats) ws_stats_tail(lds, s1, s2, p.stats, p.Ncol, m_prog, n_tile, tid, wv);
 }
 
 
@@ -787,24 +591,14 @@ __global__ __launch_bounds__(512, 2) void igemm_wsp_kernel(WsParams p) {
 // the kinds follows their chunk counts (plus the epilogue both pay per plane).
 __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
     typedef bf16_t TO;
-    constexpr int BM = 256, BN = 128;
-    constexpr int PWD = 18, NPP = PWD * PWD, NPIECE = (NPP + 7) / 8, PATCH = NPIECE * 1024;
-    constexpr int BST = BN * 128, NSB = 4;
-    constexpr int EPO = 8;
-    constexpr int MAXP = (NPIECE + 3) / 4;
-    static_assert(4 * WS_STG_WAVE <= PATCH, "epilogue staging fits a patch buffer");
-    static_assert(2 * PATCH + NSB * BST <= 160 * 1024, "patches + ring fit the CU's LDS");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * PATCH + NSB * BST];
+    constexpr int BM = WS_BM, BN = WS_BN;
+    constexpr int PWD = WSP_PWD, PATCH = WSP_PATCH, BST = WSP_BST, NSB = WSP_NSB, EPO = WS_EPO;
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[WSP_LDS];
     unsigned char* const bring = lds + 2 * PATCH;
 
     const GatherGeom& g = p.g;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-#ifdef DPC_SIMT_EMU
-    const int wv = tid >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+    const WsWave w = ws_wave_id();
+    const int tid = w.tid, lane = w.lane, wv = w.wv;
     const bool kindB = (int)blockIdx.x >= p.gm;
     const int m_prog = kindB ? (int)blockIdx.x - p.gm : (int)blockIdx.x;
     const int gmk = kindB ? p.ntn : p.gm;          // workgroups of this kind (p.ntn carries kind B's count)
@@ -824,7 +618,6 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
         // ------------------------------------------------------------------ loader waves
         const int lw = wv - 4;
         const int rl = lane >> 3;
-        const BufRsrc rs_a = make_buf_rsrc(p.src, p.src_bytes);
         const BufRsrc rs_b = make_buf_rsrc(p.wgt, p.wgt_bytes);
         const int ub = (lane & 7) ^ lds_swz1(8 * lw + rl);
         // weight-tile rows 8 (lw + 4 i) + rl: i = 0, 1 are the first class half, i = 2, 3 the second; row inside the half = output column ci
@@ -834,30 +627,7 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
             const int n = 8 * (lw + 4 * (i & 1)) + rl;
             wrow[i] = (unsigned)(n * p.ldw + ub * 8) * 2u;
         }
-        unsigned poff[MAXP];
-        DPC_UNROLL
-        for (int i = 0; i < MAXP; ++i) {
-            const int pp = 8 * (lw + 4 * i) + rl;
-            const int pr = pp / PWD, pc = pp - pr * PWD;
-            const bool ok = pp < NPP && pr >= 1 && pr <= 16 && pc >= 1 && pc <= 16;
-            const int up = (lane & 7) ^ ((pc >> 1) & 7);
-            poff[i] = ok ? (unsigned)((((pr - 1) * 16 + (pc - 1)) * g.src_ld + up * 8) * 2) : DPC_BUF_OOB;
-        }
-        const int n_mine = (NPIECE - lw + 3) / 4;
-        int issued = 0;
-        auto issue_patch = [&](int gg, int i0, int i1) {
-            const int tl = gg / G, grp = gg - tl * G;
-            const int mt = m_prog + tl * gmk;
-            const unsigned soff = (unsigned)((mt * BM * g.src_ld + grp * 64) * 2);
-            unsigned char* dst = lds + (gg & 1) * PATCH;
-            DPC_UNROLL
-            for (int i = 0; i < MAXP; ++i)
-                if (i >= i0 && i < i1 && i < n_mine) {
-                    glds16_buf(rs_a, poff[i], soff, dst + (lw + 4 * i) * 1024, lane);
-                    ++issued;
-                }
-        };
-        auto issue_b = [&](int gc) {
+        auto issue_b = [&](int gc) -> int {
             const int gg = gc / CPG, q = gc - gg * CPG;
             const int grp = gg % G;
             int sy, sx;
@@ -871,34 +641,12 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
                 const unsigned kd = (unsigned)((ky * 3 + kx) * g.Ci + grp * 64);
                 glds16_buf(rs_b, valid ? wrow[i] : DPC_BUF_OOB, kd * 2u, st + (lw + 4 * i) * 1024, lane);
             }
-            issued += 4;
+            return 4;
         };
-        // slots as in igemm_wsp_kernel: what is issued between two chunk barriers, patch pieces first, the weights of chunk c+3 last;
-        // "at most (slot c-2) + (slot c-1) operations outstanding" = the weights of chunk c, and every patch piece issued before them,
-        // have landed.  A group has only CPG = 4 / 3 chunks, and its patch must be complete at its first chunk's barrier, i.e. issued
-        // in slots <= first - 3: all of the NEXT group's pieces go out in the first CPG - 2 slots of this group.
-        const int pslots = CPG - 2, ppc = (MAXP + pslots - 1) / pslots;
-        if (total > 0) {
-            issue_patch(0, 0, MAXP);
-            issue_b(0);
-        }
-        issued = 0;
-        if (total > 1) issue_b(1);
-        int o2 = issued;
-        issued = 0;
-        if (total > 2) issue_b(2);
-        int o1 = issued;
-        for (int gc = 0; gc < total; ++gc) {
-            wait_vmcnt_upto(o1 + o2);
-            ws_barrier();  // chunk gc (and, at a group's first chunk, its patch) is published; every reader is done with chunk gc-1
-            const int gg = gc / CPG, q = gc - gg * CPG;
-            issued = 0;
-            if (q < pslots && (gg + 1) * CPG < total) issue_patch(gg + 1, ppc * q, ppc * q + ppc);
-            if (gc + 3 < total) issue_b(gc + 3);
-            o2 = o1;
-            o1 = issued;
-            if (q == CPG - 1 && (gg + 1) % G == 0) ws_barrier();  // matches the compute waves' "tile fully read" barrier
-        }
+        // A group has only CPG = 4 / 3 chunks, and its patch must be issued three slots before its first chunk: all of the NEXT
+        // group's pieces go out in the first CPG - 2 slots of this group
+        const WsPatchPlan pl = {.m_prog = m_prog, .mstride = gmk, .G = G, .cpg = CPG, .pslots = CPG - 2, .total = total};
+        ws_patch_loader(lds, p.src, p.src_bytes, g.src_ld, lane, lw, pl, 0, issue_b);
         return;
     }
 
@@ -907,15 +655,8 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
     // A fragments as in igemm_wsp_kernel: tile row r = gradient position (r >> 4, r & 15); shift (sy, sx) reads patch position
     // (r >> 4 + 1 + sy) * 18 + (r & 15) + 1 + sx; slot swizzle by (patch column >> 1) & 7
     int va[2];
-    {
-        const int pos0 = ((wv * 64 + l31) >> 4) * PWD + (l31 & 15);
-        DPC_UNROLL
-        for (int sx = 0; sx < 2; ++sx) {
-            const int dw = 1 + sx;
-            const int p7 = (((l31 & 15) + dw) >> 1) & 7;
-            va[sx] = (pos0 + dw) * 128 + ((lhi ^ p7) << 4);
-        }
-    }
+    const int dws[2] = {1, 2};
+    ws_patch_va(va, dws, wv, l31, lhi);
     const ldsa_t lds0 = ldsa(lds);
     const int vb = lds_unit_off(l31, lhi);
     const int cu = lane & 15, er = lane >> 4;
@@ -923,18 +664,10 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
     const int ccol = (cu & 7) * EPO;
 
     int gc = 0;
-#ifndef DPC_SIMT_EMU
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    ws_compute_prio();
     for (int t = 0; t < my_tiles; ++t) {
         const int mt = m_prog + t * gmk;
-        f32x16 acc[2][4];
-        DPC_UNROLL
-        for (int i = 0; i < 2; ++i)
-            DPC_UNROLL
-            for (int j = 0; j < 4; ++j)
-                DPC_UNROLL
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        f32x16 acc[2][4] = {};
         {
             FragSet f0, f1;
             ws_barrier();  // first chunk of the tile (and its patch) published
@@ -956,9 +689,7 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
                 a_pat = lds0 + ((t * G + grp) & 1) * PATCH;
                 pa = a_pat + (1 + sy) * (PWD * 128) + (sx ? va[1] : va[0]);
                 pb = lds0 + 2 * PATCH + (gc % NSB) * BST + vb;
-                // after the tile's last chunk these reads fetch nothing useful (the next tile re-reads after ITS first barrier):
-                // unconditional, so that the MFMAs stay out of a branch
-                step_il<true, 4608>(acc, f1, f0, pa, pb);
+                step_il<true, 4608>(acc, f1, f0, pa, pb);   // unconditional, as in igemm_ws_kernel
             }
             WS_RETIRE_TAIL_READS(f0);
         }
@@ -968,15 +699,11 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
         unsigned char* mine = lds + ((t * G + G - 1) & 1) * PATCH + wv * WS_STG_WAVE;
         DPC_UNROLL
         for (int i = 0; i < 2; ++i) {
-            stage_block(mine, acc[i], l31, lhi);
-            wave_lds_fence();
+            ws_stage_pass(mine, acc[i], l31, lhi);
             u32x4 ov[8];
             DPC_UNROLL
-            for (int it = 0; it < 8; ++it) {
-                const int row_l = er + 4 * it;
-                ov[it] = *(const u32x4*)(mine + row_l * WS_STG_ROW + cu * EPO * 2);
-            }
-            wave_lds_fence();
+            for (int it = 0; it < 8; ++it) ov[it] = ws_staged_unit(mine, er + 4 * it, (lane & 15) * WS_EPO);
+            wave_lds_fence();  // the next pass overwrites what this one has just read
             DPC_UNROLL
             for (int it = 0; it < 8; ++it) {
                 const int r = wv * 64 + i * 32 + er + 4 * it;
@@ -988,11 +715,7 @@ __global__ __launch_bounds__(512, 2) void igemm_wsd_kernel(WsParams p) {
     }
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-// knobs for experiments and for the small shapes of the test tiers
+// knobs, each read once per process
 static int ws_enabled() { static int v = env_int("DPC_IGEMM_WS", 1); return v; }
 static int ws_min_rows() { static int v = env_int("DPC_IGEMM_WS_MINROWS", 256 * 64); return v; }
 static int ws_max_programs() { static int v = env_int("DPC_IGEMM_WS_GM", 256); return v; }

@@ -22,9 +22,8 @@
 // TRANS_A: the A stage keeps dS's memory orientation, [k][m]: four sub-tiles of 64 k-rows x 64 m-columns (8 KB, 128-byte rows,
 // 16-byte slot XORed with 2 * (k & 3) -- wgrad2_kernel's image, conflict-free for the transpose read), one per compute wave;
 // fragments come from ds_read_b64_tr_b16 (two per operand register quad), eight reads per K step = one per MFMA gap.
-#include "ws_frag.h"
+#include "ws_common.h"
 #include "../../include/dpc_hip.h"
-#include <stdlib.h>
 
 struct GemmWsParams {
     const void* A;
@@ -40,7 +39,7 @@ struct FragSetT {   // transposed-A fragments: a quad = (lo, hi) halves from two
     u32x2 alo[2], ahi[2];
     u32x4 b[4];
 };
-template <int N> __device__ __forceinline__ void fragt_wait(FragSetT& f) {
+template <int N> __device__ __forceinline__ void frag_wait(FragSetT& f) {
     asm volatile("s_waitcnt lgkmcnt(%8)"
                  : "+v"(f.alo[0]), "+v"(f.ahi[0]), "+v"(f.alo[1]), "+v"(f.ahi[1]), "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]), "+v"(f.b[3])
                  : "n"(N)
@@ -105,13 +104,8 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
     static_assert(64 * GW_STG_ROW * 4 <= NST * STAGE, "f32 staging of the whole tile fits the ring");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NST * STAGE];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-#ifdef DPC_SIMT_EMU
-    const int wv = tid >> 6;
-#else
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
+    const WsWave w = ws_wave_id();
+    const int lane = w.lane, wv = w.wv;
     // XCD-contiguous logical id (workgroup b runs on XCD b & 7), then (column tile, row tile, slice), column tile fastest
     int id = blockIdx.x;
     {
@@ -188,16 +182,8 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
     const int l31 = lane & 31, lhi = lane >> 5;
     const ldsa_t lds0 = ldsa(lds);
     const int fb0 = BM * 128 + lds_unit_off(l31, lhi);
-    f32x16 acc[2][4];
-    DPC_UNROLL
-    for (int i = 0; i < 2; ++i)
-        DPC_UNROLL
-        for (int j = 0; j < 4; ++j)
-            DPC_UNROLL
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-#ifndef DPC_SIMT_EMU
-    __builtin_amdgcn_s_setprio(3);
-#endif
+    f32x16 acc[2][4] = {};
+    ws_compute_prio();
     if (!TRANS_A) {
         const int fa0 = lds_unit_off(wv * 64 + l31, lhi);
         FragSet f0, f1;
@@ -214,7 +200,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
             pb = lds0 + ((gc + 1) % NST) * STAGE + fb0;
             step_il<true, 4096>(acc, f1, f0, pa, pb);   // after the last chunk these reads fetch nothing useful (MFMAs stay out of a branch) ...
         }
-        frag_wait<0>(f0);                               // ... and are retired before their registers are handed on (WS_RETIRE_TAIL_READS)
+        WS_RETIRE_TAIL_READS(f0);                       // ... and are retired before their registers are handed on
     } else {
 #ifdef DPC_SIMT_EMU
         // functional form for the host simulator: same LDS image, same fragment addresses, no pipelining
@@ -263,7 +249,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
             step_il_t<1>(acc, f0, f1, a0, a1, pb ^ 32);
             step_il_t<2>(acc, f1, f0, a0, a1, pb ^ 64);
             step_il_t<3>(acc, f0, f1, a0, a1, pb ^ 96);
-            fragt_wait<0>(f1);
+            frag_wait<0>(f1);
             ws_barrier();
             const int nb = ((gc + 1) % NST) * STAGE;
             a0 = lds0 + nb + wv * 8192 + fo[0];
@@ -271,7 +257,7 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
             pb = lds0 + nb + fb0;
             step_il_t<0>(acc, f1, f0, a0, a1, pb);
         }
-        fragt_wait<0>(f0);   // the reads past the last chunk land before their registers are handed on
+        WS_RETIRE_TAIL_READS(f0);   // the reads past the last chunk land before their registers are handed on
 #endif
     }
 
@@ -301,16 +287,11 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(GemmWsParams p) {
     }
 }
 
-static int gw_env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // plans (and, with pointers, launches) the loader / compute split-K GEMM; returns 1 when the shape is not served
 static int gemm_ws_plan(int trans_a, int M, int N, int K, int lda, int ldb, GemmWsParams* p) {
-    static const int on = gw_env_int("DPC_GEMM_WS", 1);
+    static const int on = env_int("DPC_GEMM_WS", 1);
     if (!on) return 1;
-    const int min_dim = gw_env_int("DPC_GEMM_WS_MIN", 1024);                           // (read per call: the test tiers lower it for small shapes)
+    const int min_dim = env_int("DPC_GEMM_WS_MIN", 1024);                              // (read per call: the test tiers lower it for small shapes)
     if (N % 128 || lda % 8 || ldb % 8 || M < min_dim || K < min_dim) return 1;         // the contrastive head's shapes; everything else: generic kernel
     // 16-byte units must not straddle the end of an operand row.  Row-major A: K % 8 == 0.  K-major A: its rows beyond K are
     // zero-filled by the buffer bounds, so the last unit of a B row may run into the row's padding (ldb >= K rounded up, finite

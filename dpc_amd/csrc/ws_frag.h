@@ -1,8 +1,8 @@
 // ws_frag.h -- the compute-wave side of the loader / compute kernels (conv_igemm_ws.hip, gemm_ws.hip): fragment reads that hipcc
-// does not track, interleaved one per MFMA gap with hand-counted waits, and the packed epilogue staging.  Moved out of
-// conv_igemm_ws.hip in round 4 so that the split-K GEMMs of the score backward (dpc/model_3d.py:83's autograd) run on the same
-// machinery.  Everything here is about ONE invariant: an asm LDS read's destination registers stay tied ("+v") until a wait has
-// retired the read -- scripts/asm_hazard_lint.py checks the compiled code for it.
+// does not track, interleaved one per MFMA gap with hand-counted waits.  Moved out of conv_igemm_ws.hip in round 4 so that the
+// split-K GEMMs of the score backward (dpc/model_3d.py:83's autograd) run on the same machinery; what the kernels share around
+// this pipeline is in ws_common.h.  Everything here is about ONE invariant: an asm LDS read's destination registers stay tied
+// ("+v") until a wait has retired the read -- scripts/asm_hazard_lint.py checks the compiled code for it.
 #pragma once
 #include "conv_common.h"
 
@@ -55,7 +55,10 @@ template <int N> __device__ __forceinline__ void frag_wait(FragSet& f) {
 // a few hundred launches.  Claiming the whole LDS removed one way of stretching it, not the hazard.  The rule (cdna_hip_programming.md
 // "What hipcc does not do", 1): an asm load's destination must stay live, by a "+v" tie, until a wait has retired the load.
 // scripts/asm_hazard_lint.py checks the compiled code for exactly this (tests/test_asm_hazards.py); DPC_WS_NOFIX re-creates the
-// hazard in the probe library for the squatter repro (scripts/probes/squat_probe.py, profiles/r04_cotenant.txt).
+// hazard in the probe library for the squatter repro (scripts/probes/squat_probe.py, profiles/r04_cotenant.txt).  The macro is
+// the tail retirement of every kernel on this pipeline -- the three of conv_igemm_ws.hip and both paths of gemm_ws.hip (the
+// transposed one through its frag_wait overload) -- so the define reaches whichever of the two files is compiled with it; the
+// probe library compiles conv_igemm_ws.hip alone that way.
 #ifdef DPC_WS_NOFIX
 #define WS_RETIRE_TAIL_READS(f) ((void)0)
 #else
@@ -65,7 +68,7 @@ __device__ __forceinline__ void mma_step(f32x16 (&acc)[2][4], const FragSet& f) 
     DPC_UNROLL
     for (int i = 0; i < 2; ++i)
         DPC_UNROLL
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma_32x32x16_bf16(f.b[j], f.a[i], acc[i][j]);   // transposed block, see stage_block
+        for (int j = 0; j < 4; ++j) acc[i][j] = mfma_32x32x16_bf16(f.b[j], f.a[i], acc[i][j]);   // transposed block, see stage_block (ws_common.h)
 }
 
 // LDS addresses as integers (32-bit on the device: pointer arithmetic on generic pointers drags an address-space cast with a
@@ -138,20 +141,3 @@ __device__ __forceinline__ void step_il(f32x16 (&acc)[2][4], const FragSet& use,
 #undef DPC_IL_MMA
 #endif
 }
-
-// The MFMAs are issued with the operands swapped (weights as the first operand): acc[i][j] then holds the TRANSPOSED 32 x 32
-// block -- a lane owns ONE tile row (l & 31) and four consecutive output columns per register quad -- so the epilogue stages a
-// quad as one packed 8-byte LDS write (16 per 32-row pass instead of 64 two-byte writes; 37 of 347 us on layer2 were staging).
-// Staging rows are 272 bytes apart: the 16 lanes of a ds_write_b64 group then hit 16 disjoint bank pairs, and the row reads
-// (ds_read_b128, 4 rows per instruction) stay conflict-free.
-constexpr int WS_STG_ROW = 272, WS_STG_WAVE = 32 * WS_STG_ROW;
-__device__ __forceinline__ void stage_block(unsigned char* mine, const f32x16 (&acc)[4], int l31, int lhi) {
-    DPC_UNROLL
-    for (int j = 0; j < 4; ++j)
-        DPC_UNROLL
-        for (int k = 0; k < 4; ++k) {
-            u32x2 v = {bf16x2_pack(acc[j][4 * k], acc[j][4 * k + 1]), bf16x2_pack(acc[j][4 * k + 2], acc[j][4 * k + 3])};
-            *(u32x2*)(mine + l31 * WS_STG_ROW + (j * 32 + 8 * k + 4 * lhi) * 2) = v;
-        }
-}
-
