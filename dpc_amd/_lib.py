@@ -159,6 +159,11 @@ _SIGS = {
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
     "dpc_lc_test_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "dpc_lc_test_finish": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "dpc_embed_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dpc_embed_finish": [_vp, _vp, _i32, _f32, _vp, _vp],
+    "dpc_knn_ws_bytes": [_i32, _i32, _i32],
+    "dpc_knn_topk": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp],
+    "dpc_knn_recall": [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
     "dpc_stem_wgrad_fused": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
     "dpc_adam": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp],
 }

@@ -357,6 +357,29 @@ __device__ __forceinline__ void wave_lds_fence() {
 #endif
 }
 
+// Wave-wide votes and wave-uniform lane reads (retrieval.hip: a sorted list held one entry per lane).  On the device a vote is one
+// compare into a scalar register pair and a read of a uniform lane is v_readlane_b32; the host simulator builds both from its shuffle.
+// Every lane of the wave must take part.
+__device__ __forceinline__ uint64_t wave_ballot(bool p) {
+#ifdef DPC_SIMT_EMU
+    uint64_t m = p ? (1ull << simt::cur.lane) : 0ull;
+    for (int s = 32; s >= 1; s >>= 1) m |= __shfl_xor(m, s);
+    return m;
+#else
+    return __ballot(p);
+#endif
+}
+__device__ __forceinline__ int wave_read_lane(int v, int lane_uniform) {
+#ifdef DPC_SIMT_EMU
+    return __shfl(v, lane_uniform);
+#else
+    return __builtin_amdgcn_readlane(v, lane_uniform);
+#endif
+}
+__device__ __forceinline__ float wave_read_lane(float v, int lane_uniform) {
+    return __builtin_bit_cast(float, wave_read_lane(__builtin_bit_cast(int, v), lane_uniform));
+}
+
 // LDS-DMA through a buffer resource (buffer_load_dwordx4 ... offen lds): like glds16, but the source is
 // base + voff + soff with a 32-bit per-lane offset and a wave-uniform scalar offset, and a lane whose
 // offset falls outside [0, nbytes) writes 16 zero bytes to LDS (probed on MI355X, scripts/probes/buflds.*):

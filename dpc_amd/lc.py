@@ -346,12 +346,40 @@ class LCEngine(BackboneEngine):
         ``test_confusion`` the run (``test_reset`` starts one).  graph=True: the per-chunk forward is a replay of capture_eval_step()
         (the label is set once per video; the gather and the accumulation, whose arguments differ per chunk, stay eager; the engine's
         first eval-mode forward is eager, as capture_eval_step asks)."""
-        from .data import video_windows_to_input
         if not hasattr(self, "test_totals"):
             self.test_reset()
         label = int(label)
         if not 0 <= label < self.num_class:
             raise ValueError(f"label {label} is outside [0, {self.num_class})")
+        self.test_label.fill_(label)
+        if graph:
+            self.check_graph_capture()
+            self.set_labels(self.test_label)
+
+        def forward():
+            if not graph:
+                self.forward(None, self.test_label, train=False)
+            else:
+                self._eval_forward_replayed()
+
+        self._video_chunks(frames_u8, starts, clip, ds, vlen, forward, lambda n_valid: self.call(
+            "dpc_lc_test_accumulate", self.logits, self.B, n_valid, self.num_class, self.num_class, self.test_psum, self.test_lsum,
+            self.test_count))
+        self.call("dpc_lc_test_finish", self.test_psum, self.test_lsum, self.test_count, self.num_class, label, self.test_prob, self.test_res,
+                  self.test_totals, self.test_confusion)
+
+    def _eval_forward_replayed(self):
+        """the eval-mode forward on the operand and labels as they stand, as a replay of capture_eval_step() -- eagerly the first
+        time, as capture_eval_step asks"""
+        if not self._eval_ran:
+            self.forward(None, None, train=False)
+        else:
+            self.capture_eval_step()()
+
+    def _video_chunks(self, frames_u8, starts, clip: dict, ds: int, vlen: Optional[int], forward, reduce):
+        """the chunk loop of the video-level protocols: the video is uploaded ONCE; per chunk of B windows: gather into the stem's
+        operand (dpc_video_windows_to_input; the last chunk is padded by repeating its last window), forward(), reduce(valid rows)"""
+        from .data import video_windows_to_input
         starts = [int(s) for s in starts]
         if not starts:
             raise ValueError("a video without windows is skipped by the caller (data.lc_test_windows returned none)")
@@ -359,25 +387,65 @@ class LCEngine(BackboneEngine):
         video = video.to(self.device)
         vlen = video.shape[0] if vlen is None else int(vlen)
         B = self.B
-        self.test_label.fill_(label)
-        if graph:
-            self.check_graph_capture()
-            self.set_labels(self.test_label)
         for i in range(0, len(starts), B):
             st = starts[i:i + B]
             n_valid = len(st)
             st = st + [st[-1]] * (B - n_valid)
             video_windows_to_input(self.lib, video, vlen, st, clip, self.N, self.SL, ds, self.size, None, self.x_s2d)
-            if not graph:
-                self.forward(None, self.test_label, train=False)
-            elif not self._eval_ran:
+            forward()
+            reduce(n_valid)
+
+    # ---- one L2-normalised embedding per video (csrc/retrieval.hip; dpc_amd/retrieval.py looks up its neighbours)
+    def embed_video(self, frames_u8, starts, clip: dict, out_row: torch.Tensor, ds: int = 3, vlen: Optional[int] = None, graph: bool = False,
+                    bn: str = "running"):
+        """the embedding of one video into ``out_row`` (a row of a caller-owned f32 [videos, D] tensor on the engine's device): the chunk
+        loop of test_video, after each forward dpc_embed_accumulate on ``self.ctx`` (the spatial mean of the last ConvGRU state, f32
+        [B, D], before final_bn) with the chunk's valid count, then dpc_embed_finish: the mean over the windows, divided by
+        max(its 2-norm, 1e-12) (F.normalize).  Nothing crosses to the host.
+
+        bn='running': the eval-mode forward, as the video-level test uses -- right for any checkpoint of this entry, ``--train_what
+        head`` included (its frozen backbone still moved its running buffers).  graph=True replays capture_eval_step() under
+        test_video's rule.
+        bn='batch': BatchNorm3d uses the chunk's own statistics, as the reference's DPC_RNN does in eval mode -- the only sensible
+        mode for a DPC checkpoint loaded by key intersection, which carries no running statistics.  No dropout is applied (all-ones
+        masks, no draw), and the running buffers and num_batches_tracked are put back bit for bit after the last chunk.  An
+        embedding in this mode depends on the OTHER windows of its chunk, the repeated padding windows of a last chunk included:
+        another batch size, or another cut into chunks, gives another embedding.  graph=True is refused with it."""
+        if bn not in ("running", "batch"):
+            raise ValueError(f"bn = {bn!r}: 'running' or 'batch'")
+        if graph and bn == "batch":
+            raise ValueError("graph=True replays the eval-mode step: it cannot be combined with bn='batch'")
+        D, f32 = self.D, torch.float32
+        if not isinstance(out_row, torch.Tensor) or out_row.dtype != f32 or tuple(out_row.shape) != (D,) or not out_row.is_contiguous() or \
+                out_row.device != self.ctx.device:
+            raise ValueError(f"out_row must be a contiguous float32 [{D}] row on {self.ctx.device}")
+        if not hasattr(self, "emb_sum"):
+            self.emb_sum = torch.zeros(D, dtype=f32, device=self.device)
+            self.emb_count = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if graph:
+            self.check_graph_capture()
+        saved = None
+        if bn == "batch":
+            if not hasattr(self, "_ones_masks"):
+                self._ones_masks = (torch.ones(self.N, self.M, D, dtype=f32, device=self.device), torch.ones(self.B, D, dtype=f32, device=self.device))
+            saved = {k: v.clone() for k, v in self.BUF.items()}
+
+        def forward():
+            if bn == "batch":
+                self.forward(None, None, train=True, gru_masks=self._ones_masks[0], fc_mask=self._ones_masks[1])
+            elif not graph:
                 self.forward(None, None, train=False)
             else:
-                self.capture_eval_step()()
-            self.call("dpc_lc_test_accumulate", self.logits, B, n_valid, self.num_class, self.num_class, self.test_psum, self.test_lsum,
-                      self.test_count)
-        self.call("dpc_lc_test_finish", self.test_psum, self.test_lsum, self.test_count, self.num_class, label, self.test_prob, self.test_res,
-                  self.test_totals, self.test_confusion)
+                self._eval_forward_replayed()
+
+        try:
+            self._video_chunks(frames_u8, starts, clip, ds, vlen, forward, lambda n_valid: self.call(
+                "dpc_embed_accumulate", self.ctx, self.B, n_valid, D, D, self.emb_sum, self.emb_count))
+        finally:
+            if saved is not None:
+                for k, v in saved.items():
+                    self.BUF[k].copy_(v)
+        self.call("dpc_embed_finish", self.emb_sum, self.emb_count, D, 1e-12, out_row)
 
 
 class _LCOutput(torch.autograd.Function):

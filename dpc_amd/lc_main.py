@@ -36,6 +36,17 @@ epoch schedule scales every group, checkpoints written in these modes resume in 
 ``--train_what head``: only ``final_bn.*`` and ``final_fc.*`` train -- a linear probe on a frozen extractor.  The backward stops in
 front of the ConvGRU; the extractor's BatchNorm layers keep using batch statistics and updating their running buffers in train()
 (requires_grad = False in torch, and the only sensible mode after ``--pretrain``: a DPC checkpoint has no running statistics).
+
+    python -m dpc_amd.lc_main --frames q.npy --labels ql.npy [--lengths ..] --retrieval out/epoch10.pth.tar --gpu 0
+        [--gallery_frames g.npy --gallery_labels gl.npy [--gallery_lengths ..]] [--retrieval_k 1,5,10,20,50] [--retrieval_bn running|batch]
+
+``--retrieval`` (an addition of this build) answers "how good is this checkpoint?" without a fine-tuning run: one L2-normalised
+embedding per video (the mean over its test windows of the context vector ahead of ``final_bn``), cosine nearest neighbours in the
+gallery -- or leave-one-out inside the query set -- recall@k and the 1-NN confusion matrix, all on the device (csrc/retrieval.hip),
+one readback.  The checkpoint loads like ``--test`` (strict, else by key intersection, so a DPC checkpoint gives its backbone and
+ConvGRU; pass ``--retrieval_bn batch`` for one: it has no running statistics).  Prints ``R@1: .. R@5: ..  (Nq queries, Ng gallery
+videos, leave-one-out|cross, bn running|batch)``, appends it to ``retrieval_log.md`` beside the checkpoint and writes
+``<ckpt>.retrieval.npz``.
 """
 from __future__ import annotations
 
@@ -92,7 +103,85 @@ def build_parser() -> argparse.ArgumentParser:
                         'and labels are drawn on the device inside the graph (LCEngine.fill_synthetic) -- NOT the batches of a run without '
                         '--graph; with --frames the batches, parameters and log lines are those of the run without it.  With --test '
                         '--frames: the per-chunk forward of the video-level test is a replayed graph, same totals')
+    parser.add_argument('--retrieval', default='', type=str, help='checkpoint (or "random"): nearest-neighbour video retrieval instead of '
+                        'training -- one L2-normalised embedding per video of --frames (LCEngine.embed_video), cosine neighbours '
+                        '(csrc/retrieval.hip), recall@k and the 1-NN confusion matrix; loaded like --test')
+    parser.add_argument('--gallery_frames', default='', type=str, help='the gallery the queries of --frames are matched against '
+                        '(default: leave-one-out inside the query set)')
+    parser.add_argument('--gallery_labels', default='', type=str, help='labels of --gallery_frames')
+    parser.add_argument('--gallery_lengths', default='', type=str, help='lengths of --gallery_frames')
+    parser.add_argument('--retrieval_k', default='1,5,10,20,50', type=str, help='the k of recall@k, ascending, at most 64')
+    parser.add_argument('--retrieval_bn', default='running', choices=['running', 'batch'], help='BatchNorm3d of the embedding forward: '
+                        'running = eval mode, right for any checkpoint of this entry; batch = the statistics of each chunk of '
+                        'windows, for a DPC checkpoint, which carries no running statistics (an embedding then depends on its chunk)')
     return parser
+
+
+RETRIEVAL_MAX_K = 64   # dpc_knn_topk
+
+
+def retrieval_ks(text: str):
+    """--retrieval_k: ascending k values in [1, 64]"""
+    try:
+        ks = [int(k) for k in str(text).split(',') if k.strip() != '']
+    except ValueError:
+        raise ValueError('--retrieval_k wants integers separated by commas, got %r' % text) from None
+    if not ks or ks[0] < 1 or any(a >= b for a, b in zip(ks, ks[1:])):
+        raise ValueError('--retrieval_k wants ascending positive integers, got %r' % text)
+    if ks[-1] > RETRIEVAL_MAX_K:
+        raise ValueError('--retrieval_k: the neighbour search keeps at most %d neighbours, got %d' % (RETRIEVAL_MAX_K, ks[-1]))
+    return ks
+
+
+def retrieval(args, eng, mk, dev, log, num_epoch: int, probe=None):
+    """--retrieval: every video long enough for a window is embedded (file order), each query's K = max(--retrieval_k) nearest gallery
+    videos are looked up -- in --gallery_frames, or leave-one-out inside the query set -- and recall@k, the first hits and the 1-NN
+    confusion matrix [label of the neighbour][label of the query] are counted on the device; ONE readback at the end."""
+    import numpy as np
+    from . import retrieval as R
+    ks = retrieval_ks(args.retrieval_k)
+    t0 = time.time()
+
+    def embed(frames, labels, lengths):
+        src = mk(frames, labels, lengths, 'test')
+        if not src.keep:
+            raise ValueError('no video of %s is long enough for %d x %d frames at stride %d' % (frames, args.num_seq, args.seq_len, args.ds))
+        emb = torch.zeros(len(src.keep), eng.D, dtype=torch.float32, device=dev)
+        labs = []
+        for row, (_, fr, label, starts, clip) in enumerate(src.videos()):
+            eng.embed_video(fr, starts, clip, emb[row], ds=args.ds, graph=args.graph, bn=args.retrieval_bn)
+            labs.append(label)
+        return emb, torch.tensor(labs, dtype=torch.int64).to(dev), src.skipped
+
+    q_emb, q_lab, skipped = embed(args.frames, args.labels, args.lengths)
+    cross = bool(args.gallery_frames)
+    if cross:
+        g_emb, g_lab, g_skipped = embed(args.gallery_frames, args.gallery_labels, args.gallery_lengths)
+        skipped += g_skipped
+        skip = None
+    else:
+        g_emb, g_lab = q_emb, q_lab
+        skip = torch.arange(q_emb.shape[0], dtype=torch.int32).to(dev)
+    top_idx, top_sim = R.knn_topk(eng.lib, q_emb, g_emb, ks[-1], skip=skip)
+    hits, first_hit, confusion = R.recall_at_k(eng.lib, top_idx, q_lab, g_lab, ks, args.num_class)
+    nq, ng = q_emb.shape[0], g_emb.shape[0]
+    # the ONE readback of the run
+    out = {k: v.cpu().numpy() for k, v in (('query_emb', q_emb), ('gallery_emb', g_emb), ('query_labels', q_lab), ('gallery_labels', g_lab),
+                                           ('top_idx', top_idx), ('top_sim', top_sim), ('first_hit', first_hit), ('hits', hits),
+                                           ('confusion', confusion))}
+    out['ks'] = np.array(ks, np.int32)
+    out['recall'] = out.pop('hits').astype(np.float64) / nq
+    line = ' '.join('R@{}: {:.4f}'.format(k, r) for k, r in zip(ks, out['recall'])) + '  ({} queries, {} gallery videos, {}, bn {})'.format(
+        nq, ng, 'cross' if cross else 'leave-one-out', args.retrieval_bn)
+    log(line)
+    log('(retrieval checkpoint epoch {})'.format(num_epoch))
+    log('{} videos skipped (too short for {} x {} frames at stride {}), {:.1f} s'.format(skipped, args.num_seq, args.seq_len, args.ds,
+                                                                                        time.time() - t0))
+    if args.retrieval != 'random':
+        np.savez(args.retrieval + '.retrieval.npz', **out)
+        write_log(content=line, epoch=num_epoch, filename=os.path.join(os.path.dirname(args.retrieval), 'retrieval_log.md'))
+    if probe:
+        np.savez(os.path.join(probe, 'retrieval.npz'), **out)
 
 
 def write_log(content: str, epoch: int, filename: str):
@@ -185,7 +274,7 @@ def _worker(rank: int, world: int, args, port: int):
             eng.lr = lrs[-1]   # the log line's lr: the head group's
 
     set_lr(lr_multiplier(0, 0.1, milestones, 1))  # LambdaLR's constructor step
-    for path, what in ((args.test, 'test'), (args.resume, 'resume'), (args.pretrain, 'pretrain')):
+    for path, what in ((args.test, 'test'), (args.retrieval, 'test'), (args.resume, 'resume'), (args.pretrain, 'pretrain')):   # --retrieval loads like --test
         if not path or path == 'random' or (what == 'pretrain' and args.resume):
             continue
         if not os.path.isfile(path):
@@ -235,6 +324,9 @@ def _worker(rank: int, world: int, args, port: int):
         np.random.seed(rank)      # as dpc_amd.main: one stream per rank like one per loader worker (eval/test.py seeds nothing)
         mk = lambda fr, lb, ln, recipe: LabelledFrameSource(fr, lb, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu,  # noqa: E731
                                                             args.num_class, recipe, ln or None, rank, world, args.crop)
+        if args.retrieval:
+            retrieval(args, eng, mk, dev, log, num_epoch, probe)
+            return
         if args.test:
             src_test = mk(args.frames, args.labels, args.lengths, 'test')
             t0 = time.time()
@@ -374,6 +466,18 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     world = max(len(gpus), 1)
     if args.test and args.frames and world != 1:   # the reference's DataParallel over the windows of a video is not reproduced
         raise ValueError('--test with --frames runs on one GPU (the windows of a video are chunked on it): pass --gpu 0')
+    if args.retrieval:
+        if args.test:
+            raise ValueError('--retrieval and --test are two runs: pass one of them')
+        if not args.frames:
+            raise ValueError('--retrieval needs --frames and --labels')
+        if bool(args.gallery_frames) != bool(args.gallery_labels):
+            raise ValueError('--gallery_frames and --gallery_labels come together')
+        if world != 1:   # the rule of --test --frames
+            raise ValueError('--retrieval runs on one GPU (the windows of a video are chunked on it): pass --gpu 0')
+        retrieval_ks(args.retrieval_k)
+        if args.graph and args.retrieval_bn == 'batch':
+            raise ValueError('--graph replays the eval-mode step: it cannot be combined with --retrieval_bn batch')
     if _simulator is not None and world != 1:
         raise ValueError('the simulator runs one rank')
     if world == 1:

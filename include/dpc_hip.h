@@ -500,6 +500,32 @@ int dpc_lc_test_accumulate(const float* logits, int32_t rows, int32_t n_valid, i
 int dpc_lc_test_finish(float* psum, float* lsum, int32_t* count, int32_t num_class, int32_t label, float* mean_prob, float* video,
                        double* totals, int64_t* confusion, dpc_stream_t stream);
 
+/* ---- nearest-neighbour video retrieval (csrc/retrieval.hip) ------------------------------------------------------------------------
+ * Per-video state on the device: esum [D] (the context vectors of the windows so far, summed), count [1] -- zero before the first
+ * video, cleared by dpc_embed_finish.
+ * dpc_embed_accumulate: ctx f32 [rows][ld >= D]; rows [0, n_valid) are added in row order, rows beyond n_valid are never read.
+ * dpc_embed_finish: m = esum / count, out[d] = m[d] / max(||m||_2, eps) (F.normalize); count == 0: nothing is written.
+ * dpc_knn_topk: Q f32 [nq][ldq], G f32 [ng][ldg], sim(i, j) = sum_d Q[i][d] G[j][d] on the exact-f32 matrix instruction in ascending
+ *   d; per query the K best gallery rows by (sim descending, index ascending) -> top_idx int32 [nq][K], top_sim f32 [nq][K]; slots
+ *   without a candidate hold -1 / -inf.  skip int32 [nq] (NULL = none): query i never returns row skip[i].  The gallery is cut into
+ *   n_slabs slabs (0 = chosen from nq, ng and the CU count; 1..64 forced), one workgroup per (32 queries, slab) writes a partial list
+ *   into ws (dpc_knn_ws_bytes(nq, K, n_slabs) bytes: with n_slabs == 0 enough for whatever ng turns out to be), a second kernel merges
+ *   them: the same bits for every n_slabs.  D a multiple of 32 in [32, 256], 1 <= K <= 64, rows 16-byte aligned, else
+ *   DPC_ERR_UNSUPPORTED.  Inputs must be finite.
+ * dpc_knn_recall: labels int64; ks int32 [nk] ascending, each <= K; first_hit int32 [nq] = 0-based rank of the first neighbour with
+ *   the query's label (-1: none; slots holding -1 are ignored); hits int64 [nk] += #{i : 0 <= first_hit[i] < ks[j]}; confusion int64
+ *   [num_class][num_class]: confusion[g_label[top_idx[i][0]]][q_label[i]] += 1 where a first neighbour exists.
+ * No atomics, no allocation, no host synchronisation: same inputs, same bits. */
+int dpc_embed_accumulate(const float* ctx, int32_t rows, int32_t n_valid, int32_t D, int32_t ld, float* esum, int32_t* count,
+                         dpc_stream_t stream);
+int dpc_embed_finish(float* esum, int32_t* count, int32_t D, float eps, float* out, dpc_stream_t stream);
+int dpc_knn_ws_bytes(int32_t nq, int32_t K, int32_t n_slabs);
+int dpc_knn_topk(const float* Q, int32_t nq, int32_t ldq, const float* G, int32_t ng, int32_t ldg, int32_t D, int32_t K,
+                 const int32_t* skip, int32_t n_slabs, float* top_sim, int32_t* top_idx, void* ws, int64_t ws_bytes, dpc_stream_t stream);
+int dpc_knn_recall(const int32_t* top_idx, int32_t nq, int32_t K, const int64_t* q_label, const int64_t* g_label, int32_t ng,
+                   int32_t num_class, const int32_t* ks, int32_t nk, int64_t* hits, int32_t* first_hit, int64_t* confusion,
+                   dpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
