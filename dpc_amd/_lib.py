@@ -75,6 +75,17 @@ class Resample(C.Structure):
     _fields_ = [("xb", C.c_void_p), ("xk", C.c_void_p), ("yb", C.c_void_p), ("yk", C.c_void_p), ("ksx", C.c_int32), ("ksy", C.c_int32)]
 
 
+class RecipeDesc(C.Structure):
+    """struct dpc_recipe_desc (include/dpc_hip.h)"""
+    _fields_ = ([(n, C.c_double) for n in ("sized_p", "gray_p", "jitter_p", "brightness", "contrast", "saturation", "hue")] +
+                [("flip_code", C.c_int32), ("reserved", C.c_int32)])
+
+
+def recipe_slots(n_frames: int) -> int:
+    """DPC_RECIPE_SLOTS (include/dpc_hip.h): uniforms one clip of n_frames frames owns"""
+    return 58 + 9 * n_frames
+
+
 class PackEntry(C.Structure):
     """struct dpc_pack_entry (include/dpc_hip.h)"""
     _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("d0", C.c_int32), ("d1", C.c_int32), ("d2", C.c_int32), ("block0", C.c_int32),
@@ -157,6 +168,10 @@ _SIGS = {
                                C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
     "dpc_video_windows_to_input": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(Resample),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp],
+    "dpc_store_to_input": [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(Resample), _vp, _vp, _vp,
+                           C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp, _vp],
+    "dpc_draw_recipe": [C.POINTER(RecipeDesc), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_uint64, _vp, _vp,
+                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dpc_lc_test_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "dpc_lc_test_finish": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_embed_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],

@@ -45,6 +45,8 @@ struct Geo {
     const int32_t *xtab, *ytab;
     const int32_t *xb, *xk, *yb, *yk;  // [B][W][2], [B][W][ksx], [B][H][2], [B][H][ksy]
     int ksx, ksy;
+    // packed frame store (dpc_store_to_input): index, in `frames`, of the first frame of the video clip b reads; NULL = b * clip_pitch
+    const long long* clip_first;
 };
 
 __device__ __forceinline__ int clip8(int v) {
@@ -54,7 +56,9 @@ __device__ __forceinline__ int clip8(int v) {
 
 // the three channels of output pixel (y, x) of frame (b, f): crop / flip / resize, then the RandomGray channel choice
 __device__ __forceinline__ void geo_pixel(const Geo& g, int b, int f, int gch, const dpc_clip_aug& a, int y, int x, int (&rgb)[3]) {
-    const uint8_t* fr = g.frames + ((long long)b * g.clip_pitch + f) * g.H0 * g.W0 * 3;
+    // 64-bit throughout: a resident store is larger than 2^31 bytes
+    const long long fi = g.clip_first ? g.clip_first[b] + f : (long long)b * g.clip_pitch + f;
+    const uint8_t* fr = g.frames + fi * g.H0 * g.W0 * 3;
     // flip = 1: flip AFTER crop (+ resize) (the k400 recipe); flip = 2: flip of the full frame BEFORE the crop (ucf101)
     const int xo = a.flip == 1 ? g.W - 1 - x : x;
     if (g.xb) {
@@ -317,17 +321,18 @@ extern "C" int dpc_frames_to_input(const uint8_t* frames, int32_t B, int32_t F, 
     return dpc_launch_status();
 }
 
-extern "C" int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t F, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
-                                      const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
-                                      const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3,
-                                      const float* std3, float* block, void* s2d, int32_t dtype_s2d, dpc_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// what dpc_frames_to_input_ex and dpc_store_to_input share: clip_first == nullptr is the dense [B][F] array
+static int frames_ex_launch(const uint8_t* frames, int32_t B, int32_t F, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                            const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
+                            const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3,
+                            const float* std3, float* block, void* s2d, int32_t dtype_s2d, const long long* clip_first, hipStream_t stream) {
     if (int rc = check_common(frames, B, F, H0, W0, aug, N, SL, ds, H, W, mean3, std3, block, s2d)) return rc;
     if (jitter && (!u8_ws || !lsum_ws)) return DPC_ERR_ARG;
     if (rs && (!rs->xb || !rs->xk || !rs->yb || !rs->yk || rs->ksx <= 0 || rs->ksy <= 0)) return DPC_ERR_ARG;
     if (s2d && dtype_s2d != DPC_F32 && dtype_s2d != DPC_BF16) return DPC_ERR_ARG;
     Geo g = {frames, B, F, H0, W0, F, aug, gray, N, SL, ds, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
     if (rs) { g.xb = rs->xb; g.xk = rs->xk; g.yb = rs->yb; g.yk = rs->yk; g.ksx = rs->ksx; g.ksy = rs->ksy; }
+    g.clip_first = clip_first;
     const long long cells = (long long)B * N * SL * (H / 2) * (W / 2);
     const unsigned grid = grid_cells(cells);
     const bool bf = s2d && dtype_s2d == DPC_BF16;
@@ -351,6 +356,29 @@ extern "C" int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t 
                    mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], block, (float*)s2d);
     }
     return dpc_launch_status();
+}
+
+extern "C" int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t F, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                                      const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
+                                      const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3,
+                                      const float* std3, float* block, void* s2d, int32_t dtype_s2d, dpc_stream_t stream_) {
+    return frames_ex_launch(frames, B, F, H0, W0, aug, gray, N, SL, ds, H, W, rs, jitter, u8_ws, lsum_ws, mean3, std3, block, s2d, dtype_s2d,
+                            nullptr, (hipStream_t)stream_);
+}
+
+// The packed frame store (dpc_amd/data.py FrameStore): `store` u8 [total_frames][H0][W0][3] holds videos of any length back to back,
+// clip b reads frames clip_first[b] + aug[b].start + (n * SL + sl) * ds of it.  clip_first and aug are device tables (dpc_draw_recipe
+// writes them from the store's offsets, so every frame lies inside its video); nothing here can check them without a host round trip.
+extern "C" int dpc_store_to_input(const uint8_t* store, int32_t B, int64_t total_frames, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                                  const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
+                                  const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3,
+                                  const float* std3, float* block, void* s2d, int32_t dtype_s2d, const int64_t* clip_first,
+                                  dpc_stream_t stream_) {
+    if (!clip_first || total_frames <= 0) return DPC_ERR_ARG;
+    if (N > 0 && SL > 0 && ds > 0 && (long long)(N * SL - 1) * ds >= total_frames) return DPC_ERR_ARG;   // not one clip fits
+    // (F = 1 below: the dense array's clip pitch, unused once clip_first is set)
+    return frames_ex_launch(store, B, 1, H0, W0, aug, gray, N, SL, ds, H, W, rs, jitter, u8_ws, lsum_ws, mean3, std3, block, s2d, dtype_s2d,
+                            (const long long*)clip_first, (hipStream_t)stream_);
 }
 
 // The test protocol of eval/dataset_3d_lc.py:109-127 without replicating frames: `video` is ONE video [F][H0][W0][3] that every

@@ -28,11 +28,13 @@ __device__ __host__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t 
 // keep (value 1/(1-p)) iff the 24-bit uniform u = word >> 8 satisfies u >= p * 2^24  (P[keep] = 1 - p)
 // `stream` (counter word c2) separates independent mask streams drawn under one (seed, step): 0 = the ConvGRU's carried state,
 // 1 = the classifier head's Dropout(0.5) (eval/model_3d_lc.py:42), 2 = the synthetic N(0,1) input (csrc/synthetic.hip), 3 = the
-// synthetic class labels (csrc/labels.hip) -- never seed + k, which would collide with rank k's stream.
+// synthetic class labels (csrc/labels.hip), 4 = the augmentation draws of resident frames (csrc/recipe_draw.hip) -- never seed + k,
+// which would collide with rank k's stream.
 #define DPC_PHILOX_STREAM_GRU 0u
 #define DPC_PHILOX_STREAM_LC_FC 1u
 #define DPC_PHILOX_STREAM_INPUT 2u
 #define DPC_PHILOX_STREAM_LABEL 3u
+#define DPC_PHILOX_STREAM_AUG 4u
 __device__ __host__ __forceinline__ void dropout_keep4(uint64_t seed, uint32_t step, uint32_t blk, uint32_t thresh24, float inv_keep, float* out4,
                                                        uint32_t stream = DPC_PHILOX_STREAM_GRU) {
     const Philox4 r = philox4x32_10(blk, step, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));

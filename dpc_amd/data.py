@@ -344,6 +344,301 @@ def recipe_to_input(lib: L.Lib, frames: torch.Tensor, starts, clips: "List[dict]
     return block, s2d
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# frames resident in HBM (`--resident`): packed store, the recipes as descriptors, their draws from given uniforms
+# ------------------------------------------------------------------------------------------------------------------
+_JITTER = dict(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.25, p=1.0)
+RECIPES = {   # dpc/main.py:114-132 as the fields of dpc_recipe_desc (include/dpc_hip.h); sized_p None = RandomCrop(crop) + NEAREST Scale
+    "k400": dict(sized_p=1.0, flip_code=1, gray_p=0.5, jitter=_JITTER),
+    "ucf101": dict(sized_p=None, flip_code=2, gray_p=0.5, jitter=_JITTER),
+}
+# The descriptor does not preclude the fine-tuning recipes (LC_RECIPES: sized_p 1.0 / 0.3 / 0.0, no gray, jitter p 0.3); what they
+# need beyond it is ColorJitter(consistent=True) (one draw copied to every frame) and the NEAREST Scale behind the sized crop.
+SLOT_START, SLOT_FLIP, SLOT_SIZED_P, SLOT_CROP_X, SLOT_CROP_Y, SLOT_JITTER_P, SLOT_ATTEMPT, SLOT_FRAME = 0, 1, 2, 3, 4, 5, 8, 58
+ATTEMPT_SLOTS, FRAME_SLOTS = 5, 9   # include/dpc_hip.h (dpc_draw_recipe) documents the layout
+recipe_slots = L.recipe_slots
+
+
+def recipe_desc(recipe) -> "L.RecipeDesc":
+    r = RECIPES[recipe] if isinstance(recipe, str) else recipe
+    j = r.get("jitter") or {}
+    neg = lambda v: -1.0 if v is None else float(v)   # noqa: E731
+    return L.RecipeDesc(neg(r.get("sized_p")), neg(r.get("gray_p")), float(j.get("p", 1.0)) if r.get("jitter") else -1.0,
+                        float(j.get("brightness", 0)), float(j.get("contrast", 0)), float(j.get("saturation", 0)), float(j.get("hue", 0)),
+                        int(r.get("flip_code", 0)), 0)
+
+
+def resident_ks(recipe, W0: int, H0: int, size: int) -> int:
+    """pitch of the coefficient tables dpc_draw_recipe writes: the widest window any crop box of a W0 x H0 frame can need,
+    2 ceil(max(W0, H0) / size) + 1 (resample_tables: ksize = 2 ceil(in / out) + 1 with in <= max(W0, H0)); an index map has one tap"""
+    r = RECIPES[recipe] if isinstance(recipe, str) else recipe
+    return 1 if r.get("sized_p") is None else 2 * -(-max(W0, H0) // size) + 1
+
+
+def recipe_from_uniforms(recipe, u, vlen: int, W0: int, H0: int, crop: int, size: int, n_frames: int, span: int):
+    """The draws of one clip made from a given row of uniforms: u[slot] in [0, 1), ``recipe_slots(n_frames)`` of them in the slot
+    layout of dpc_draw_recipe (include/dpc_hip.h), the decisions of ``draw_k400`` / ``draw_ucf101`` and of ``idx_sampler``
+    (span = num_seq * seq_len * ds; the start is uniform on [0, vlen - span)).  randint(0, n) = floor(u (n + 1)), uniform(a, b) =
+    a + (b - a) u, a rejected crop attempt keeps its slots: a pure function of the row, whichever branch is taken.  Returns the dict
+    ``draw_k400`` returns plus ``start``.  csrc/recipe_draw.hip makes the same decisions with the same double arithmetic on the
+    device (bit for bit, tests/resident_cases.py); fed to ``recipe_to_input`` it gives a --frames run the recipes of a --resident run."""
+    r = RECIPES[recipe] if isinstance(recipe, str) else recipe
+    u = [float(v) for v in u]
+    if len(u) != recipe_slots(n_frames):
+        raise ValueError(f"{recipe_slots(n_frames)} uniforms per clip of {n_frames} frames, got {len(u)}")
+    if vlen - span <= 0:
+        raise ValueError("video too short (dataset_3d.py:87 drops it)")
+    randint = lambda s, n: int(math.floor(u[s] * (n + 1)))   # noqa: E731
+    uniform = lambda s, a, b: a + (b - a) * u[s]             # noqa: E731  (random.uniform)
+    start = int(math.floor(u[SLOT_START] * (vlen - span)))
+    code = int(r.get("flip_code", 0))
+    flip = code if code and u[SLOT_FLIP] < 0.5 else 0
+    ident = np.arange(size, dtype=np.int32)
+    x1 = y1 = 0
+    if r.get("sized_p") is None:                                # RandomCrop(crop) -> Scale((size, size)) [NEAREST]
+        if crop > W0 or crop > H0:
+            raise ValueError(f"RandomCrop({crop}) of {W0} x {H0} frames leaves the frame")
+        if not (W0 == crop and H0 == crop):
+            x1, y1 = randint(SLOT_CROP_X, W0 - crop), randint(SLOT_CROP_Y, H0 - crop)
+        xt = _tables_from_index(nearest_tables(crop, size) if crop != size else ident)
+        yt = (xt[0].copy(), xt[1].copy())
+    elif u[SLOT_SIZED_P] < r["sized_p"]:                        # RandomSizedCrop (_draw_sized_crop with the uniforms of the slots)
+        xt = None
+        for a in range(10):
+            s = SLOT_ATTEMPT + ATTEMPT_SLOTS * a
+            target_area = uniform(s, 0.5, 1) * (W0 * H0)
+            aspect = uniform(s + 1, 3. / 4, 4. / 3)
+            w = int(round(math.sqrt(target_area * aspect)))
+            h = int(round(math.sqrt(target_area / aspect)))
+            if u[s + 2] < 0.5:
+                w, h = h, w
+            if w <= W0 and h <= H0:
+                x1, y1 = randint(s + 3, W0 - w), randint(s + 4, H0 - h)
+                xt, yt = resample_tables(w, size), resample_tables(h, size)
+                break
+        if xt is None:
+            if W0 < H0:
+                ow, oh = size, int(size * H0 / W0)
+            else:
+                oh, ow = size, int(size * W0 / H0)
+            cx, cy = int(round((ow - size) / 2.)), int(round((oh - size) / 2.))
+            xt, yt = resample_tables(W0, ow, cx, size), resample_tables(H0, oh, cy, size)
+    else:                                                       # the failed `p` draw: CenterCrop(size)
+        if W0 < size or H0 < size:
+            raise ValueError(f"CenterCrop({size}) of {W0} x {H0} frames leaves the frame (PIL would pad with black; not reproduced)")
+        x1, y1 = int(round((W0 - size) / 2.)), int(round((H0 - size) / 2.))
+        xt, yt = _tables_from_index(ident), _tables_from_index(ident)
+    gray = np.full(n_frames, -1, np.int8)
+    jit = (FrameJitter * n_frames)()
+    jitter, gray_p = r.get("jitter"), r.get("gray_p")
+    jit_on = jitter is not None and u[SLOT_JITTER_P] < jitter.get("p", 1.0)
+    for f in range(n_frames):
+        s = SLOT_FRAME + FRAME_SLOTS * f
+        if gray_p is not None and u[s] < gray_p:
+            gray[f] = int(math.floor(u[s + 1] * 3))
+        j = jit[f]
+        j.order[:] = [255, 255, 255, 255]
+        if not jit_on:
+            continue
+        ops: List[int] = []
+        for op, name in enumerate(("brightness", "contrast", "saturation", "hue")):   # _jitter_get_params
+            v = jitter.get(name, 0)
+            if not v:
+                continue
+            lo, hi = (-v, v) if name == "hue" else (max(0.0, 1.0 - v), 1.0 + v)
+            fac = uniform(s + 2 + op, lo, hi)
+            if name == "hue":
+                j.hue_shift = int(fac * 255) & 0xFF
+            else:
+                j.factor[op] = fac
+            ops.append(op)
+        for i in range(len(ops) - 1, 0, -1):                    # Fisher-Yates from the top, as random.shuffle walks
+            q = int(math.floor(u[s + 6 + (3 - i)] * (i + 1)))
+            ops[i], ops[q] = ops[q], ops[i]
+        for k, op in enumerate(ops):
+            j.order[k] = op
+    return dict(start=start, x1=x1, y1=y1, flip=flip, xb=xt[0], xk=xt[1], yb=yt[0], yk=yt[1], gray=gray, jitter=jit)
+
+
+def free_device_memory(device) -> int:
+    """bytes of device memory still free (the one place FrameStore.to_device asks; tests replace it)"""
+    device = torch.device(device)
+    return int(torch.cuda.mem_get_info(device)[0]) if device.type == "cuda" else 1 << 62
+
+
+def _load(a, mmap=False):
+    if isinstance(a, (str, bytes)) or hasattr(a, "__fspath__"):
+        return np.load(a, mmap_mode="r") if mmap else np.load(a)
+    return a
+
+
+class FrameStore:
+    """Decoded videos of ANY length packed back to back: frames uint8 [total_frames, H0, W0, 3] and offsets int64 [videos + 1]
+    (non-decreasing, offsets[0] == 0, offsets[-1] == total_frames), video v = frames[offsets[v]:offsets[v + 1]].  Built from such a
+    packed array with its offsets (``--frames packed.npy --offsets offsets.npy``) or from the dense [clips, F, H0, W0, 3] array of
+    ``FrameSource`` (every video F frames, offsets = arange(clips + 1) * F).  ``to_device`` uploads it ONCE; after that a training
+    step reads its frames from HBM (dpc_store_to_input) and nothing crosses the host per step."""
+
+    def __init__(self, frames, offsets=None):
+        fr = _load(frames, mmap=True)
+        if getattr(fr, "dtype", None) != np.uint8 or fr.ndim not in (4, 5) or fr.shape[-1] != 3:
+            raise ValueError("--frames wants a uint8 array [clips, F, H0, W0, 3], or with --offsets a packed [total_frames, H0, W0, 3]")
+        if fr.ndim == 5:
+            if offsets is not None:
+                raise ValueError("--offsets goes with a packed 4-D array [total_frames, H0, W0, 3]; this --frames array is the dense 5-D one")
+            offsets = np.arange(fr.shape[0] + 1, dtype=np.int64) * fr.shape[1]
+            fr = fr.reshape((-1,) + tuple(fr.shape[2:]))
+        elif offsets is None:
+            raise ValueError("a packed 4-D --frames array [total_frames, H0, W0, 3] needs --offsets (int64 [videos + 1]): the flag is missing")
+        off = np.asarray(_load(offsets))
+        if off.ndim != 1 or off.shape[0] < 2 or not np.issubdtype(off.dtype, np.integer):
+            raise ValueError(f"--offsets wants integers [videos + 1], got shape {off.shape} and type {off.dtype}")
+        off = off.astype(np.int64)
+        if int(off[0]) != 0 or (np.diff(off) < 0).any():
+            raise ValueError("--offsets must start at 0 and never decrease")
+        if int(off[-1]) != fr.shape[0]:
+            raise ValueError(f"--offsets ends at {int(off[-1])} but the store holds {fr.shape[0]} frames")
+        self.frames, self.offsets = fr, off
+        self.H0, self.W0 = int(fr.shape[1]), int(fr.shape[2])
+        self.dev: Optional[torch.Tensor] = None
+        self.offsets_dev: Optional[torch.Tensor] = None
+
+    def __len__(self):
+        return self.offsets.shape[0] - 1
+
+    @property
+    def total_frames(self) -> int:
+        return int(self.frames.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return self.total_frames * self.H0 * self.W0 * 3
+
+    def long_enough(self, span: int) -> np.ndarray:
+        """videos with vlen - span > 0, span = num_seq * seq_len * ds (dpc/dataset_3d.py:80-82 drops the others)"""
+        return np.nonzero(np.diff(self.offsets) - span > 0)[0]
+
+    def to_device(self, device, reserve: int = 0, chunk_bytes: int = 64 << 20):
+        """one upload, in chunks through ONE pinned staging buffer (no second host copy of the store).  `reserve` = bytes the engine
+        still has to allocate beside it.  Every rank calls this: each GPU holds a whole copy of the store."""
+        device = torch.device(device)
+        if self.dev is not None:
+            if self.dev.device != device:
+                raise ValueError(f"the store already lives on {self.dev.device}")
+            return self
+        free = free_device_memory(device)
+        if self.nbytes + reserve > free:
+            raise ValueError(f"the frame store needs {self.nbytes} bytes of device memory but only {free - reserve} are available "
+                             f"({free} free, {reserve} still to be allocated by the engine): --resident holds every frame in HBM")
+        dev = torch.empty((self.total_frames, self.H0, self.W0, 3), dtype=torch.uint8, device=device)
+        flat, src, n = dev.view(-1), self.frames.reshape(-1), self.nbytes
+        stage = torch.empty(max(1, min(chunk_bytes, n)), dtype=torch.uint8, pin_memory=device.type == "cuda")
+        host = stage.numpy()
+        for o in range(0, n, stage.numel()):
+            m = min(stage.numel(), n - o)
+            host[:m] = src[o:o + m]
+            flat[o:o + m].copy_(stage[:m])   # blocking: the staging buffer is free again when it returns
+        self.dev, self.offsets_dev = dev, torch.from_numpy(self.offsets).to(device)
+        return self
+
+
+class ResidentFrameSource:
+    """``FrameSource`` for a store that lives in HBM (``python -m dpc_amd.main --frames ... --resident``).  The epoch order stays
+    on the host (``torch.randperm``, as RandomSampler); ONCE per epoch this rank's slice of it, int32 [steps * B] video indices,
+    is copied into a device buffer of fixed size and a device cursor is zeroed.  Per step ``BackboneEngine.load_resident``
+    advances the cursor and the draw counter, draws the recipe on the device (dpc_draw_recipe: Philox stream 4 keyed by `seed`
+    and the draw counter -- NOT the draws of Python's ``random``: a different, equally distributed sample than ``FrameSource``
+    makes) and gathers (dpc_store_to_input): no host synchronisation, no copy, no allocation, no address that changes, so one
+    captured step serves every epoch.  Every rank holds the WHOLE store (any rank may draw any video): one copy per GPU.
+    The draw counter is not part of a checkpoint (the engine keeps none of its counters there): a resumed run sets it from the
+    steps already taken (``set_draw``), which is what it would have been."""
+
+    def __init__(self, store: FrameStore, dataset: str, num_seq: int, seq_len: int, ds: int, size: int, batch: int, device, rank: int = 0,
+                 world: int = 1, crop: int = 224, seed: int = 0):
+        if dataset not in RECIPES:
+            raise ValueError("dataset not supported")   # dpc/main.py:301
+        if store.dev is None:
+            raise ValueError("upload the store first (FrameStore.to_device)")
+        self.store, self.dataset, self.N, self.SL, self.size, self.batch, self.rank, self.world = store, dataset, num_seq, seq_len, size, batch, rank, world
+        self.ds = 5 if dataset == "k400" else ds           # dpc/main.py:294, :299
+        self.n_fr = num_seq * seq_len
+        self.crop, self.seed = (crop if dataset == "ucf101" else size), int(seed) & 0xFFFFFFFFFFFFFFFF
+        H0, W0 = store.H0, store.W0
+        if dataset == "ucf101" and (H0 < crop or W0 < crop):
+            raise ValueError(f"the ucf101 recipe crops {crop} x {crop} (dpc/main.py:117): frames of {W0} x {H0} are too small")
+        self.keep = store.long_enough(self.n_fr * self.ds)
+        self.skipped = len(store) - len(self.keep)
+        if len(self.keep) == 0:
+            raise ValueError(f"every one of the {len(store)} videos is too short for {num_seq} x {seq_len} frames at stride {self.ds} "
+                             "(dpc/dataset_3d.py:80-82 drops such videos)")
+        if len(self) == 0:
+            raise ValueError(f"{len(self.keep)} videos do not fill one batch of {batch} x {world}")
+        dev = self.device = store.dev.device
+        B, n_fr = batch, self.n_fr
+        self.desc = recipe_desc(dataset)
+        self.KS = resident_ks(dataset, W0, H0, size)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
+        self.perm, self.cursor, self.draw = z(len(self) * B, torch.int32), z(1, torch.int32), z(1, torch.int32)
+        self.aug, self.clip_first, self.gray = z((B, 4), torch.int32), z(B, torch.int64), z((B, n_fr), torch.int8)
+        self.jitter = z(B * n_fr * C.sizeof(FrameJitter), torch.uint8)
+        self.xb, self.yb = z((B, size, 2), torch.int32), z((B, size, 2), torch.int32)
+        self.xk, self.yk = z((B, size, self.KS), torch.int32), z((B, size, self.KS), torch.int32)
+        self.scale_tab = torch.from_numpy(nearest_tables(self.crop, size)).to(dev) if self.crop != size else None
+        self.rs = L.Resample(self.xb.data_ptr(), self.xk.data_ptr(), self.yb.data_ptr(), self.yk.data_ptr(), self.KS, self.KS)
+        self.has_jitter = self.desc.jitter_p >= 0
+
+    def __len__(self):   # batches per epoch, drop_last
+        return len(self.keep) // (self.batch * self.world)
+
+    def set_draw(self, steps: int):
+        """a resumed run: the draw counter after `steps` steps of this source"""
+        self.draw.fill_(int(steps))
+
+    def begin_epoch(self) -> np.ndarray:
+        """a new permutation: this rank's video indices int32 [steps, B] go to the device buffer, the cursor to 0"""
+        order = self.keep[torch.randperm(len(self.keep)).numpy()]     # RandomSampler: torch's generator, seeded by torch.manual_seed(0)
+        gb, B = self.batch * self.world, self.batch
+        mine = np.stack([order[i * gb + self.rank * B: i * gb + (self.rank + 1) * B] for i in range(len(self))]).astype(np.int32)
+        self.perm.copy_(torch.from_numpy(mine.reshape(-1)))
+        self.cursor.zero_()
+        return mine
+
+    def draw_recipe(self, lib: L.Lib, uniforms: Optional[torch.Tensor] = None, video_idx: Optional[torch.Tensor] = None, call=None):
+        """dpc_draw_recipe into this source's tables for the batch the cursor points at (video_idx given: that batch, cursor unused)"""
+        st = self.store
+        args = (C.byref(self.desc), self.perm if video_idx is None else video_idx, self.cursor if video_idx is None else None, st.offsets_dev,
+                self.batch, st.W0, st.H0, self.crop, self.size, self.N, self.SL, self.ds, self.KS, self.scale_tab, self.seed, self.draw,
+                uniforms, self.aug, self.clip_first, self.gray, self.jitter, self.xb, self.xk, self.yb, self.yk)
+        if call is not None:
+            return call("dpc_draw_recipe", *args)
+        return lib.call("dpc_draw_recipe", *args, lib.stream())
+
+
+def store_to_input(lib: L.Lib, store: torch.Tensor, aug: torch.Tensor, clip_first: torch.Tensor, gray: Optional[torch.Tensor], rs,
+                   jitter: Optional[torch.Tensor], num_seq: int, seq_len: int, ds: int, size: int, block: Optional[torch.Tensor] = None,
+                   s2d: Optional[torch.Tensor] = None, u8_ws: Optional[torch.Tensor] = None, lsum_ws: Optional[torch.Tensor] = None, call=None):
+    """dpc_store_to_input: store u8 [total_frames,H0,W0,3] and the device tables of one batch (aug int32 [B,4], clip_first int64 [B],
+    gray int8 [B,N*SL] or None, rs = L.Resample over [B] tables or None, jitter = dpc_frame_jitter bytes or None with its two
+    workspaces) -> block and / or the stem's operand.  The tables are trusted: dpc_draw_recipe wrote them."""
+    if store.dim() != 4 or store.shape[3] != 3 or store.dtype != torch.uint8 or not store.is_contiguous():
+        raise ValueError("store must be contiguous uint8 [total_frames,H0,W0,3]")
+    B = aug.shape[0]
+    if aug.dtype != torch.int32 or tuple(aug.shape) != (B, 4) or clip_first.dtype != torch.int64 or tuple(clip_first.shape) != (B,):
+        raise ValueError("aug int32 [B,4], clip_first int64 [B]")
+    n_fr = num_seq * seq_len
+    if jitter is not None and (u8_ws is None or lsum_ws is None or u8_ws.numel() < B * n_fr * size * size * 3 or lsum_ws.numel() < B * n_fr):
+        raise ValueError("jitter needs u8_ws (B*N*SL*size*size*3 bytes) and lsum_ws (B*N*SL int64)")
+    mean, std = (C.c_float * 3)(*MEAN), (C.c_float * 3)(*STD)
+    args = (store, B, store.shape[0], store.shape[1], store.shape[2], aug, gray, num_seq, seq_len, ds, size, size,
+            C.byref(rs) if rs is not None else None, jitter, u8_ws if jitter is not None else None, lsum_ws if jitter is not None else None,
+            mean, std, block, s2d, L.dtype_code(s2d.dtype) if s2d is not None else L.F32, clip_first)
+    if call is not None:
+        call("dpc_store_to_input", *args)
+    else:
+        lib.call("dpc_store_to_input", *args, lib.stream())
+    return block, s2d
+
+
 class FrameSource:
     """Decoded clips as ONE uint8 array [clips, F, H0, W0, 3] (``np.load(path, mmap_mode='r')`` or an array) -- the data source of
     ``python -m dpc_amd.main --frames``.  It stands where the reference has ``dataset[index]`` under

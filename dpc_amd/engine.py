@@ -603,7 +603,8 @@ class BackboneEngine:
         self.x_s2d = self.empty((BN, seq_len, H // 2, H // 2, 16), dt)
         # synthetic-input draw counter (fill_synthetic): advanced in front of every draw, read by dpc_synthetic_input on the device
         self.dev_input = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.stem = _ConvBN(self, "backbone.conv1.weight", "backbone.bn1", 16, widths[0], (1, 4, 4), (1, 1, 1), (0, 2, 2),
+        self._resident_ws = None   # load_resident's jitter workspaces (u8 image, per-frame L sums): allocated by its first call
+        self.stem =_ConvBN(self, "backbone.conv1.weight", "backbone.bn1", 16, widths[0], (1, 4, 4), (1, 1, 1), (0, 2, 2),
                             (BN, seq_len, H // 2, H // 2), stem=True)
         hp = (H // 2 - 1) // 2 + 1
         self.pool_shape = (BN, seq_len, hp, hp)
@@ -947,6 +948,33 @@ class BackboneEngine:
         stem's operand.  Follow with forward(None, ...) / train_step(None, ...)."""
         from .data import recipe_to_input
         recipe_to_input(self.lib, frames, starts, clips, self.N, self.SL, ds, self.size, None, self.x_s2d)
+
+    def resident_reserve(self) -> int:
+        """bytes this engine still allocates once frames are resident: load_resident's two jitter workspaces, and an allowance
+        of 1 GiB for the gradient scratch and graph pools that the first steps and a capture fill lazily"""
+        n = self.B * self.N * self.SL
+        return n * self.size * self.size * 3 + n * 8 + (1 << 30)
+
+    def load_resident(self, source):
+        """one batch from frames resident in HBM (data.ResidentFrameSource): advance the source's cursor and draw counter, draw the
+        recipe on the device (dpc_draw_recipe), gather from the store into the stem's operand (dpc_store_to_input).  Six launches
+        (two counters, the draw, the gather's three; its one without ColorJitter); no host synchronisation, no host-to-device copy, no allocation after the
+        first call, no address that changes: graph-safe as the `refill` of capture_train_step / capture_eval_step, and one capture
+        serves every epoch.  Follow with forward(None, ...) / train_step(None, ...)."""
+        from .data import store_to_input
+        if source.batch != self.B or source.N != self.N or source.SL != self.SL or source.size != self.size or source.device != self.device:
+            raise ValueError("the source was built for another batch / clip shape / device than this engine")
+        if source.has_jitter and self._resident_ws is None:   # allocated once, shared by every source of this engine
+            n = self.B * self.N * self.SL
+            self._resident_ws = (torch.empty(n * self.size * self.size * 3, dtype=torch.uint8, device=self.device),
+                                 torch.empty(n, dtype=torch.int64, device=self.device))
+        u8, ls = self._resident_ws if source.has_jitter else (None, None)
+        self.call("dpc_counter_advance", source.cursor)
+        self.call("dpc_counter_advance", source.draw)
+        source.draw_recipe(self.lib, call=self.call)
+        store_to_input(self.lib, source.store.dev, source.aug, source.clip_first, source.gray, source.rs,
+                       source.jitter if source.has_jitter else None, self.N, self.SL, source.ds, self.size, None, self.x_s2d, u8, ls,
+                       call=self.call)
 
     def fill_synthetic(self, seed: int, block: Optional[torch.Tensor] = None):
         """a new synthetic N(0,1) batch drawn on the device (csrc/synthetic.hip): advances dev_input, then writes the stem's operand

@@ -10,7 +10,9 @@ are averaged with one RCCL all-reduce (dpc_amd/parallel.py).  Datasets / augment
 (SURVEY.md §2 rows 8,9,11): the input is the synthetic N(0,1) video of ``--synthetic`` batches per
 epoch with the dataset's tensor layout [B, num_seq, 3, seq_len, H, W] (dpc/dataset_3d.py:109-111), or -- ``--frames clips.npy`` --
 decoded uint8 frames [clips, F, H0, W0, 3] on which the training transform of ``--dataset`` (dpc/main.py:114-132) runs on the GPU
-(dpc_amd/data.py FrameSource -> engine.load_recipe -> train_step(None): SURVEY.md §8 f4).
+(dpc_amd/data.py FrameSource -> engine.load_recipe -> train_step(None): SURVEY.md §8 f4).  ``--resident`` uploads that array (or,
+with ``--offsets``, a packed store of videos of any length) to HBM once and draws the transform on the device
+(data.ResidentFrameSource -> engine.load_resident): no host work per step; a different, equally distributed sample of clips.
 ``--graph`` runs every step after a short eager warm-up as a replay of one captured train step and one captured validation step
 (DESIGN.md §9.5.1); the synthetic input is then drawn on the device inside the graph (engine.fill_synthetic) instead of by torch.randn.
 Checkpoints are the reference's dictionary (``module.``-prefixed state_dict incl. alias keys, torch-Adam-layout
@@ -63,6 +65,13 @@ def build_parser() -> argparse.ArgumentParser:
                         'prints the replayed steps\' ms/step after each training epoch.  Synthetic input is then drawn on the device inside '
                         'the graph (engine.fill_synthetic, seed 1000 + rank) instead of by torch.randn: the batches differ from a run '
                         'without --graph.  --frames input is unchanged: the same draws and bit-identical results.  HIP device only')
+    parser.add_argument('--resident', action='store_true', help='hold the --frames array in HBM (uploaded once; every GPU holds a whole copy) '
+                        'and draw the training transform on the device: per step nothing crosses the host, and --graph replays the draw '
+                        'and the gather with the step.  The draws come from Philox (stream 4, seeded per rank), not from Python\'s random: '
+                        'the clips are a different, equally distributed sample than a run without --resident sees.  Needs --frames')
+    parser.add_argument('--offsets', default='', type=str, help='int64 .npy [videos + 1]: --frames is then a packed uint8 array '
+                        '[total_frames, H0, W0, 3] of videos of any length, video v = frames[offsets[v]:offsets[v + 1]].  Needs --resident')
+    parser.add_argument('--val_offsets', default='', type=str, help='--offsets of the --val_frames array')
     return parser
 
 
@@ -176,21 +185,46 @@ def _worker(rank: int, world: int, args, port: int):
         random.seed(rank)
         np.random.seed(rank)      # dpc/main.py:51 seeds 0; one stream per rank like one per loader worker
         mk = lambda path: FrameSource(path, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu, rank, world, args.crop)  # noqa: E731
-        src_train = mk(args.frames)
-        src_val = mk(args.val_frames) if args.val_frames else src_train
+        if args.resident:   # the store goes to HBM once; validation reads it (or its own) through a second source with its own draw stream
+            from .data import FrameStore, ResidentFrameSource
+            store = FrameStore(args.frames, args.offsets or None).to_device(dev, reserve=eng.resident_reserve())
+            store_val = (FrameStore(args.val_frames, args.val_offsets or None).to_device(dev, reserve=eng.resident_reserve())
+                         if args.val_frames else store)
+            # Philox keys: the rank in the low word, the role (0 train, 1 validation) in the high one -- never seed + k (csrc/philox.h)
+            mk = lambda st, role: ResidentFrameSource(st, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu, dev, rank,  # noqa: E731
+                                                      world, args.crop, seed=(role << 32) | rank)
+            src_train, src_val = mk(store, 0), mk(store_val, 1)
+            # the draw counters are not in the checkpoint (the engine keeps none of its counters there): a resumed run derives them
+            # from the epochs already run, which is what they were
+            src_train.set_draw(args.start_epoch * len(src_train))
+            src_val.set_draw(args.start_epoch * len(src_val))
+            if rank == 0 and (src_train.skipped or src_val.skipped):
+                print('{0} training / {1} validation videos skipped (too short for one clip)'.format(src_train.skipped, src_val.skipped), flush=True)
+        else:
+            if args.offsets or args.val_offsets:
+                raise ValueError('--offsets describes a packed frame store, which only --resident reads: --resident is missing')
+            src_train = mk(args.frames)
+            src_val = mk(args.val_frames) if args.val_frames else src_train
 
     # --graph: per run, the first `warm[train]` steps of each kind run eagerly, then ONE captured step per kind is replayed.  Synthetic
     # input: `refill` draws the batch on the device in front of the step (inside the graph once captured); --frames: load_recipe fills
-    # the operand eagerly before each step and the graph starts from it
+    # the operand eagerly before each step and the graph starts from it; --resident: `refill` advances the source's cursor, draws
+    # the recipe and gathers from the store, all on the device (engine.load_resident) -- in front of every eager step and inside the graph
     warm, captured = {True: 2, False: 1}, {True: None, False: None}
     refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
+    refills = {True: refill, False: refill}
+    if args.resident:
+        refills = {True: lambda: eng.load_resident(src_train), False: lambda: eng.load_resident(src_val)}
 
     def run_epoch(train: bool, epoch: int):
         losses, accs = AverageMeter(), [AverageMeter() for _ in range(3)]
         nonlocal iteration
         src = src_train if train else src_val
         n_batches = len(src) if src is not None else args.synthetic
-        feed = src.epoch(dev) if src is not None else None
+        feed = src.epoch(dev) if src is not None and not args.resident else None
+        refill = refills[train]
+        if args.resident:
+            src.begin_epoch()   # the epoch's permutation to the device, the cursor to 0: the one host-to-device copy of the epoch
         replayed, ev0, ev1 = 0, None, None
         for idx in range(n_batches):
             tic = time.time()
@@ -198,13 +232,13 @@ def _worker(rank: int, world: int, args, port: int):
             if feed is not None:
                 frames, starts, clips = next(feed)
                 eng.load_recipe(frames, starts, clips, ds=src.ds)   # fills the stem's operand; no f32 video in between
-            elif not args.graph:
+            elif not args.graph and not args.resident:
                 block = torch.randn(shape, device=dev, generator=gen)
             replay = args.graph and warm[train] == 0
             if args.graph and not replay:   # eager warm-up step
                 warm[train] -= 1
-                if refill is not None:
-                    refill()
+            if not replay and refill is not None:
+                refill()
             if replay:
                 if captured[train] is None:
                     captured[train] = (eng.capture_train_step(None, allreduce=allreduce, warmup=0, refill=refill) if train
@@ -266,6 +300,8 @@ def _worker(rank: int, world: int, args, port: int):
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
+    if args.resident and not args.frames:
+        raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')
     gpus = [g for g in str(args.gpu).split(',') if g != '']
     world = max(len(gpus), 1)
     if _simulator is not None and world != 1:

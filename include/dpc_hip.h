@@ -478,6 +478,48 @@ int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t F, int32_t 
                            const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3, const float* std3,
                            float* block, void* s2d, int32_t dtype_s2d, dpc_stream_t stream);
 
+/* ---- frames resident in HBM (dpc_amd/data.py FrameStore, `--resident`) -------------------------------------------------------
+ * dpc_store_to_input: dpc_frames_to_input_ex on the packed store u8 [total_frames][H0][W0][3] (videos of any length back to back):
+ *   clip b reads frame clip_first[b] + aug[b].start + (n*SL + sl)*ds, addressed in 64-bit arithmetic (a store exceeds 2^31 bytes).
+ *   clip_first int64 [B] and aug are DEVICE tables nobody can check without a host round trip: dpc_draw_recipe writes them from
+ *   the store's offsets.  Same launches as dpc_frames_to_input_ex (three with jitter, one without).
+ * dpc_draw_recipe: the random draws of one batch of the pre-training recipes (dpc/main.py:114-132) on the device, written as
+ *   exactly the tables the gather reads: aug [B], clip_first [B], gray [B][N*SL], jitter [B][N*SL], xb / yb [B][size][2],
+ *   xk / yk [B][size][KS] (zero beyond a row's taps).  Clip b reads video video_idx[(step_dev ? step_dev[0] - 1 : 0) * B + b],
+ *   whose frames are [offsets[v], offsets[v + 1]) of the store (the caller has dropped videos with no legal start).
+ *   Uniform number `slot` of clip b is u = (w >> 8) 2^-24 with w = word slot & 3 of
+ *   philox4x32_10(slot >> 2, draw_dev[0], DPC_PHILOX_STREAM_AUG, b; lo(seed), hi(seed)), or uniforms[b * DPC_RECIPE_SLOTS(N*SL) +
+ *   slot] when `uniforms` (f32, device) is given: a pure function of (seed, counter, clip, slot) whichever branch is taken.
+ *   randint(0, n) = floor(u (n + 1)); uniform(a, b) = a + (b - a) u in double.  Slots (a rejected crop attempt keeps its five):
+ *     0 start in [0, vlen - N*SL*ds)      1 flip (< 1/2)      2 RandomSizedCrop's p      3 RandomCrop x1      4 RandomCrop y1
+ *     5 ColorJitter's p                   6, 7 unused
+ *     8 + 5a + {0 area U(0.5, 1), 1 aspect U(3/4, 4/3), 2 swap (< 1/2), 3 x1, 4 y1}    attempt a = 0 .. 9
+ *     58 + 9f + {0 gray (< gray_p), 1 gray channel floor(3u), 2 brightness, 3 contrast, 4 saturation, 5 hue,
+ *                6, 7, 8 the Fisher-Yates steps i = 3, 2, 1 (j = floor(u (i + 1)), swap i and j) of the chain}    frame f
+ *   The double arithmetic is that of data.resample_tables / data._draw_sized_crop, unfused (data.recipe_from_uniforms is the host
+ *   statement of the same decisions; the two agree bit for bit).  sized_p >= 0: RandomSizedCrop(size, BILINEAR, p = sized_p) (its
+ *   ten attempts, the Scale + CenterCrop fallback, CenterCrop(size) when p fails); sized_p < 0: RandomCrop(crop) and, when crop !=
+ *   size, the NEAREST Scale as the device index table scale_tab int32 [size] (data.nearest_tables; NULL = identity).  gray_p < 0 /
+ *   jitter_p < 0: the recipe has no RandomGray / ColorJitter; a jitter range of 0 leaves that step out of the chain.  flip_code:
+ *   what aug.flip holds when the flip is drawn (1 after the crop, 2 before it; 0 = the recipe never flips).  One jitter draw per
+ *   frame (consistent=False), which is what both pre-training recipes use.
+ *   KS >= 2 ceil(max(W0, H0) / size) + 1, B <= 1024, size <= 1024. */
+#define DPC_RECIPE_SLOTS(n_frames) (58 + 9 * (n_frames))
+typedef struct dpc_recipe_desc {
+    double sized_p, gray_p, jitter_p;
+    double brightness, contrast, saturation, hue;
+    int32_t flip_code, reserved;
+} dpc_recipe_desc;
+int dpc_store_to_input(const uint8_t* store, int32_t B, int64_t total_frames, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
+                       const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
+                       const dpc_frame_jitter* jitter, uint8_t* u8_ws, uint64_t* lsum_ws, const float* mean3, const float* std3,
+                       float* block, void* s2d, int32_t dtype_s2d, const int64_t* clip_first, dpc_stream_t stream);
+int dpc_draw_recipe(const dpc_recipe_desc* recipe, const int32_t* video_idx, const int32_t* step_dev, const int64_t* offsets,
+                    int32_t B, int32_t W0, int32_t H0, int32_t crop, int32_t size, int32_t N, int32_t SL, int32_t ds, int32_t KS,
+                    const int32_t* scale_tab, uint64_t seed, const int32_t* draw_dev, const float* uniforms, dpc_clip_aug* aug,
+                    int64_t* clip_first, int8_t* gray, dpc_frame_jitter* jitter, int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk,
+                    dpc_stream_t stream);
+
 /* The test-time windows of eval/dataset_3d_lc.py:109-127 from ONE resident video: `video` u8 [F][H0][W0][3] is read by every clip
  * of the batch, clip b = the window whose first frame is aug[b].start (aug[b].flip as above; the test transform never flips).
  * dpc_frames_to_input_ex without gray / jitter; rs [B] tables as there (NULL = plain crop of H x W at (x1, y1)).  The caller has
