@@ -22,7 +22,8 @@ reference's state_dict layout and are repacked (K-contiguous, compute dtype) onc
 per optimizer step.
 
 In file order: KernelTimer and the cost model; the conv unit and the block; ``BackboneEngine``, what the DPC-RNN step and the
-LC classifier (lc.LCEngine) share, the capture machinery of their replayed steps included; ``DPCEngine``: the contrastive head, then its captured steps.
+LC classifier (lc.LCEngine) share, their captured steps included (capture_train_step / capture_eval_step over the heads'
+``_forward_loss`` / ``_backward_reaches_backbone``; entry.StepDriver is what replays them in a run); ``DPCEngine``: the contrastive head.
 """
 from __future__ import annotations
 
@@ -1170,7 +1171,7 @@ class BackboneEngine:
             if allreduce is not None:
                 allreduce(self.flat_g)
 
-    # ------------------------------------------------------------------ captured steps: what both heads' capture_* share
+    # ------------------------------------------------------------------ captured steps of both heads
     def _baked_scalars(self) -> tuple:
         """host scalars a captured step carries as kernel arguments (a replay keeps the values of its capture)"""
         gd = self.gru_desc
@@ -1262,6 +1263,105 @@ class BackboneEngine:
         self._captures[key] = replay
         return replay
 
+    def _forward_loss(self, block: Optional[torch.Tensor], train: bool):
+        """the head's forward of an engine-owned step on `block` (None: the stem's operand as it stands): leaves the metrics in
+        ``self.result`` and, when `train`, the loss gradient where ``backward()`` expects it"""
+        raise NotImplementedError
+
+    def _backward_reaches_backbone(self) -> bool:
+        """whether the engine-owned step's backward runs the backbone's backward.  A head whose backward can stop in front of it
+        answers from its optimizer's state; a captured step asks when it is captured, and the answer is part of its key."""
+        return True
+
+    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
+        """Captures the head's whole train step -- forward + loss on `block` (a static device buffer: refill it in place between
+        replays), backward, Adam -- into hipGraphs and returns ``replay() -> self.result`` (device f32: DPC loss, top1, top3, top5;
+        LC loss, top-1).  Dropout masks and Adam's bias corrections are keyed on device-side counters, so every replay is a new
+        optimizer step.
+        block=None: the step starts from the stem's operand as it stands (train_step(None)) -- and, for LC, the labels as they
+        stand in ``self.target``: filled in the graph by ``refill=lambda: eng.fill_synthetic(seed)``, or eagerly before each replay
+        (load_recipe, set_labels).
+        refill: optional callable captured in FRONT of the step (e.g. ``lambda: block.normal_()``: a fresh synthetic batch per replay
+        from torch's graph-safe default generator -- SURVEY section 8d "generated ON DEVICE").
+
+        Cached by (static input buffer, exchange, carve-out, side_off, refill identity, no_grad_params, baked host scalars): asking
+        again returns the replay that exists.  Every host scalar the capture bakes into kernel arguments (_baked_scalars: lr, wd,
+        dropouts and seeds, the Adam segment table) is part of the key, and a replay raises once one of them changed: after
+        eng.lr = ... (LR schedule, checkpoint.resume, --reset_lr) asking again captures a step with the new values instead of
+        handing back the stale replay.  The graphs are parked, never destroyed (_LIVE_GRAPHS).
+
+        One graph without data parallelism.  With the two-bucket gradient exchange the capture is cut where the backward hands the
+        gradient tail to RCCL: graph A (forward, loss, backward down to layer2) -> allreduce.start(tail) asynchronously -> graph B
+        (layer1 + stem backward) -> allreduce.finish(head) + join -> graph C (Adam).  With a backward that stops in front of the
+        backbone (_backward_reaches_backbone) there is nothing between the two exchange points, so the capture is cut ONCE: graph A
+        (forward, head backward) -> allreduce.start(tail) -> allreduce.finish(empty first bucket), as the eager step does -> graph
+        B (Adam).  No empty hipGraph is created or replayed."""
+        buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
+        need_backbone = self._backward_reaches_backbone()
+        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
+               id(refill) if refill is not None else None, tuple(sorted(self.no_grad_params))) + self._baked_scalars()
+        two_bucket = allreduce is not None and hasattr(allreduce, "start")
+        split = self.grad_split if need_backbone else 0   # the first bucket of the exchange: empty when the backward was truncated
+        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:split], self.flat_g, self.result
+
+        def warm():
+            for _ in range(warmup):
+                self.train_step(block, allreduce=allreduce)
+
+        def body(cut):
+            self._forward_loss(block, True)
+            if two_bucket and not need_backbone:   # backward() hands the tail over and returns: one cut serves both exchange points
+                self.backward(on_tail_ready=lambda _tail: None)
+                cut()
+            else:
+                self.backward(on_tail_ready=cut if two_bucket else None)
+                if allreduce is not None:
+                    cut()
+            host_steps = self._step_count
+            self.adam_step()
+            self._step_count = host_steps  # capture executes nothing
+
+        def run(eng, graphs):
+            graphs[0].replay()
+            if two_bucket:
+                allreduce.start(tail)
+                if need_backbone:
+                    graphs[1].replay()
+                allreduce.finish(head)
+                graphs[-1].replay()
+            elif allreduce is not None:
+                allreduce(whole)
+                graphs[1].replay()
+            eng._step_count += 1
+            eng.packed_for_step = -1
+            return result
+
+        # block=buf: the static input buffer stays alive (and its address un-reused) as long as the capture does
+        return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
+                             refill, block=buf)
+
+    def capture_eval_step(self, refill=None):
+        """Captures one evaluation step on the stem's operand (and LC's labels) as they stand -- `refill` (e.g. ``lambda:
+        eng.fill_synthetic(seed)``), then the head's eval-mode forward + loss -- into one hipGraph and returns ``replay() ->
+        self.result``.  The weight repack is inside the graph unconditionally, so a replay after more training evaluates the weights
+        (and running buffers) of now, not those of the capture.  Same rules as capture_train_step.  No eager warm-up: run one eager
+        evaluation step first (the forward allocates its ReLU masks on first use)."""
+        key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
+        result = self.result
+
+        def warm():
+            if self._pack_table is None:
+                self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
+
+        def body(cut):
+            self._forward_loss(None, False)
+
+        def run(eng, graphs):
+            graphs[0].replay()
+            return result
+
+        return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
+
     def release_captures(self):
         """forget this engine's captured train steps (the next capture_train_step captures again).  The hipGraphs are parked until the
         interpreter exits, not destroyed -- see _LIVE_GRAPHS for why and for what that costs; DPC_KEEP_GRAPHS=0 destroys them here,
@@ -1273,7 +1373,7 @@ class BackboneEngine:
 
 
 class DPCEngine(BackboneEngine):
-    """the DPC-RNN step: backbone + ConvGRU aggregate / predict, contrastive score, loss, and the captured steps"""
+    """the DPC-RNN step: backbone + ConvGRU aggregate / predict, contrastive score, loss"""
 
     def __init__(self, network: str = "resnet18", sample_size: int = 128, num_seq: int = 8, seq_len: int = 5,
                  pred_step: int = 3, batch: int = 4, device="cuda", compute_dtype=torch.float32,
@@ -1491,86 +1591,15 @@ class DPCEngine(BackboneEngine):
         self.call("dpc_colsum", self.dP1, dc, D, P * M, D, Gm["network_pred.0.bias"], 0, self.part, self.part.numel())
         self.call("dpc_colsum", self.dP2, dc, D, P * M, D, Gm["network_pred.2.bias"], 0, self.part, self.part.numel())
 
-    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
-        """Captures the whole train step on `block` (a static device buffer: refill it in place between replays) into
-        hipGraphs and returns ``replay() -> device f32[4]``.  One graph without data parallelism; with the two-bucket
-        gradient exchange the capture is cut where the backward hands the gradient tail to RCCL, so the replay is
-        graph A (forward, loss, backward down to layer2) -> all-reduce(tail) asynchronously -> graph B (layer1 + stem
-        backward) -> all-reduce(head) + join -> graph C (Adam).  Dropout masks and Adam's bias corrections are keyed on
-        the device-side step counter, so every replay is a new optimizer step.
-        block=None: the step starts from the stem's operand as it stands (train_step(None)): filled in the graph by
-        ``refill=lambda: eng.fill_synthetic(seed)``, or eagerly before each replay (load_recipe)."""
-        # every host scalar the capture bakes into kernel arguments is part of the key (dpc_adam_dev takes lr / wd by value, the
-        # recurrence descriptor p_drop / seed): after eng.lr = ... (LR schedule, checkpoint.resume, --reset_lr) asking again captures
-        # a step with the new values instead of handing back the stale replay (ADVICE r5)
-        # refill: optional callable captured in FRONT of the step (e.g. ``lambda: block.normal_()``: a fresh synthetic batch per replay
-        # from torch's graph-safe default generator -- SURVEY section 8d "generated ON DEVICE"); part of the key by identity
-        buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
-        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
-               id(refill) if refill is not None else None) + self._baked_scalars()
-        two_bucket = allreduce is not None and hasattr(allreduce, "start")
-        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:self.grad_split], self.flat_g, self.result
-
-        def warm():
-            for _ in range(warmup):
-                self.train_step(block, allreduce=allreduce)
-
-        def body(cut):
-            self.forward(block, train=True, materialise=False)
-            self.loss_topk(with_grad=True)
-            self.backward(on_tail_ready=cut if two_bucket else None)
-            if allreduce is not None:
-                cut()
-            host_steps = self._step_count
-            self.adam_step()
-            self._step_count = host_steps  # capture executes nothing
-
-        def run(eng, graphs):
-            graphs[0].replay()
-            if two_bucket:
-                allreduce.start(tail)
-                graphs[1].replay()
-                allreduce.finish(head)
-                graphs[2].replay()
-            elif allreduce is not None:
-                allreduce(whole)
-                graphs[1].replay()
-            eng._step_count += 1
-            eng.packed_for_step = -1
-            return result
-
-        # block=buf: the static input buffer stays alive (and its address un-reused) as long as the capture does
-        return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
-                             refill, block=buf)
-
-    def capture_eval_step(self, refill=None):
-        """Captures one validation step on the stem's operand -- `refill` (e.g. ``lambda: eng.fill_synthetic(seed)``), then
-        forward(None, train=False, materialise=False) + loss_topk(with_grad=False) -- into one hipGraph and returns
-        ``replay() -> device f32[4]``.  The weight repack is inside the graph unconditionally, so a replay after more training
-        evaluates the weights of now, not those of the capture.  Same rules as capture_train_step: the baked host scalars are part
-        of the cache key, the graph is parked (_LIVE_GRAPHS), never destroyed while the process runs.  No eager warm-up: run one
-        eager validation step first (the forward allocates its ReLU masks on first use)."""
-        key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
-        result = self.result
-
-        def warm():
-            if self._pack_table is None:
-                self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
-
-        def body(cut):
-            self.forward(None, train=False, materialise=False)
-            self.loss_topk(with_grad=False)
-
-        def run(eng, graphs):
-            graphs[0].replay()
-            return result
-
-        return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
+    def _forward_loss(self, block: Optional[torch.Tensor], train: bool, dropout_masks: Optional[torch.Tensor] = None):
+        """forward without a score to return (consumed by the loss: bf16 logits, or never written) + CE / top-k.
+        dropout_masks: train_step's explicit masks (tests)"""
+        self.forward(block, train=train, dropout_masks=dropout_masks, materialise=False)
+        self.loss_topk(with_grad=train)
 
     def train_step(self, block: torch.Tensor, dropout_masks: Optional[torch.Tensor] = None, allreduce=None) -> torch.Tensor:
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""
-        self.forward(block, train=True, dropout_masks=dropout_masks, materialise=False)
-        res = self.loss_topk(with_grad=True)
+        self._forward_loss(block, True, dropout_masks=dropout_masks)
         self._backward_and_exchange(allreduce)
         self.adam_step()
-        return res
+        return self.result

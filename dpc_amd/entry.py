@@ -1,0 +1,118 @@
+"""What the two command-line entries (dpc_amd.main, dpc_amd.lc_main) share and neither owns: starting one process per GPU
+(``launch``), bringing a rank up (``open_rank``), averaging the logged metrics (``average_over_ranks``) and ``StepDriver``, the
+``--graph`` protocol of a run -- a short eager warm-up per kind of step, then one captured step per kind, replayed
+(engine.BackboneEngine.capture_train_step / capture_eval_step).  Argument checks, engines, checkpoints, data
+sources, schedules and log lines stay in the entries.
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+
+
+def world_size(args) -> int:
+    """one rank per id of ``--gpu 0,1,..``"""
+    return max(len([g for g in str(args.gpu).split(',') if g != '']), 1)
+
+
+def launch(worker, args):
+    """``worker(rank, world, args, port)`` in this process for one GPU, else in one spawned process per GPU"""
+    world = world_size(args)
+    if world == 1:
+        worker(0, 1, args, 0)
+    else:
+        import torch.multiprocessing as mp
+        mp.spawn(worker, args=(world, args, 29500 + os.getpid() % 2000), nprocs=world, join=True)
+
+
+def open_rank(rank: int, world: int, args, port: int):
+    """(device, simulator handle or None, torch.distributed or None) of this rank: its GPU made current and, for world > 1, the
+    process group -- RCCL bound to the device, or gloo between the simulator's rank processes (CPU tier)"""
+    gpus = [int(g) for g in str(args.gpu).split(',') if g != '']
+    sim = getattr(args, '_simulator', None)   # tests only (CPU tier): the host-side SIMT simulator handle; the command line cannot set it
+    if sim == 'emu':   # a spawned rank of the CPU tier loads its own handle (a ctypes library does not pickle)
+        from . import _lib
+        sim = _lib.load_emulator()
+    dev = torch.device('cpu') if sim is not None else torch.device('cuda', gpus[rank] if world > 1 else gpus[0])
+    if sim is None:
+        torch.cuda.set_device(dev)
+    if world <= 1:
+        return dev, sim, None
+    import torch.distributed as dist
+    if sim is None:
+        dist.init_process_group('nccl', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world, device_id=dev)
+    else:
+        torch.set_num_threads(max(1, (os.cpu_count() or 2) // (2 * world)))
+        dist.init_process_group('gloo', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world)
+    return dev, sim, dist
+
+
+def average_over_ranks(dist, vals: torch.Tensor, world: int) -> torch.Tensor:
+    """mean over ranks of a small device tensor, in place (the logged loss / top-k: equal shards, so the mean of per-rank means is the
+    reference's mean over the gathered rows, dpc/main.py:211-218).  RCCL averages in the collective; gloo (CPU tier) has no AVG."""
+    if dist is None or world <= 1:
+        return vals
+    if dist.get_backend() == 'nccl':
+        dist.all_reduce(vals, op=dist.ReduceOp.AVG)
+    else:
+        dist.all_reduce(vals, op=dist.ReduceOp.SUM)
+        vals.div_(world)
+    return vals
+
+
+class StepDriver:
+    """The steps of a run, eager or replayed.  Without ``graph`` every step is eager.  With it, per RUN (not per epoch) the first two
+    train steps and the first validation step are eager -- they size every lazy buffer --; from then on the engine is asked once
+    per kind for a captured step on the stem's operand (``warmup=0``) and every later step replays that handle.
+
+    ``refill_train`` / ``refill_val`` fill the operand on the device (fill_synthetic, load_resident): called in front of an eager
+    step, handed to the capture -- which runs them inside the graph -- for a replayed one.  Nothing here touches the GPU until a step
+    replays; the timing events are made on the epoch's first replayed train step."""
+
+    def __init__(self, eng, graph: bool, allreduce=None, refill_train=None, refill_val=None):
+        self.eng, self.graph, self.allreduce = eng, bool(graph), allreduce
+        self.refill = {True: refill_train, False: refill_val}
+        self.warm = {True: 2, False: 1}
+        self.invalidate()
+        self.replayed, self.events = 0, None
+
+    def invalidate(self):
+        """drop the handles: the next step of each kind asks the engine again -- which hands back the replay that exists when nothing
+        it bakes in has changed, and captures a new step otherwise (a new learning rate).  The warm-up is not repeated."""
+        self.captured = {True: None, False: None}
+
+    def step(self, train: bool, eager, before_replay=None):
+        """one train / validation step -> (its device result, whether it was a replay).  ``eager()`` is the entry's own step, run
+        when this one is not replayed; ``before_replay()`` is host work a replay needs in front of it and an eager step does itself"""
+        refill = self.refill[train]
+        if not self.graph or self.warm[train]:
+            if self.graph:
+                self.warm[train] -= 1
+            if refill is not None:
+                refill()
+            return eager(), False
+        if before_replay is not None:
+            before_replay()
+        if self.captured[train] is None:
+            self.captured[train] = (self.eng.capture_train_step(None, allreduce=self.allreduce, warmup=0, refill=refill) if train
+                                    else self.eng.capture_eval_step(refill))
+        if train and self.events is None:
+            self.events = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.events[0].record()
+        res = self.captured[train]()
+        if train:
+            self.events[1].record()
+            self.replayed += 1
+        return res, True
+
+    def replay_line(self, batch_size: int):
+        """ends a training epoch: its ``Graph replay:`` line -- device time from the first replayed train step of the epoch to the end
+        of its last one -- or None when none was replayed"""
+        n, events = self.replayed, self.events
+        self.replayed, self.events = 0, None
+        if not n:
+            return None
+        events[1].synchronize()
+        ms = events[0].elapsed_time(events[1]) / n
+        return 'Graph replay: {0} steps, {1:.3f} ms/step, {2:.1f} clips/s'.format(n, ms, batch_size * 1e3 / ms)

@@ -9,7 +9,9 @@ Same 2d3d-ResNet and ConvGRU kernels as the DPC-RNN step; what differs from ``DP
   * head: spatial mean -> BatchNorm1d -> Dropout(p) -> Linear(num_class); loss = CrossEntropyLoss on the clip label,
     accuracy = top-1 (eval/test.py:244-255).
 
-``LCEngine`` is the static-schedule engine (forward / backward / fused Adam on flat arenas, like ``DPCEngine``);
+``LCEngine`` is the static-schedule engine (forward / backward / fused Adam on flat arenas, like ``DPCEngine``; its captured steps
+are ``BackboneEngine.capture_train_step`` / ``capture_eval_step``, which it serves through ``_forward_loss`` and
+``_backward_reaches_backbone``);
 ``LC`` is the drop-in ``nn.Module`` with the reference's constructor, ``forward(block) -> (output, context)`` and
 state_dict keys (running buffers included), so ``--pretrain`` of a DPC checkpoint and ``--test`` files load by key.
 In train mode the module's outputs carry an autograd node (``_LCOutput``), so the training lines of eval/test.py:224-255 run
@@ -235,6 +237,15 @@ class LCEngine(BackboneEngine):
         self.call("dpc_relu_tpool_bwd", self.blocks[-1].out, self.d_featrelu, dc, B, N, self.feat_shape[1], SQ, D, self.d_feat)
         self._backbone_backward(self.d_feat, on_tail_ready)
 
+    def _forward_loss(self, block: Optional[torch.Tensor], train: bool):
+        """the CE kernel is the last launch of forward(); the labels are those in ``self.target``"""
+        self.forward(block, None, train=train)
+
+    def _backward_reaches_backbone(self) -> bool:
+        """grad_wanted() of the engine-owned step: the optimizer's groups and no_grad_params decide.  A frozen backbone truncates
+        the backward, and the two-bucket exchange of such a step has an empty first bucket (_first_bucket)"""
+        return self.grad_wanted()[0]
+
     def train_step(self, block: torch.Tensor, target: Optional[torch.Tensor] = None, allreduce=None, **masks) -> torch.Tensor:
         """forward + CE / accuracy + backward (+ gradient all-reduce) + Adam; returns device f32[2] = loss, top-1.
         target=None: the labels as they stand in ``self.target``"""
@@ -243,88 +254,10 @@ class LCEngine(BackboneEngine):
         self.adam_step()
         return self.result
 
-    # ---- captured steps (engine.BackboneEngine._capture): DPCEngine's contract on the classifier's step
     def _baked_scalars(self) -> tuple:
+        """a captured step (engine.BackboneEngine.capture_train_step / capture_eval_step) also carries the head's dropout and seed"""
         hd = self.head_desc
         return super()._baked_scalars() + (float(hd.p_drop), int(hd.seed))
-
-    def capture_train_step(self, block: Optional[torch.Tensor], allreduce=None, warmup: int = 2, refill=None):
-        """Captures forward(block, None, train=True) + backward + Adam into hipGraphs and returns ``replay() -> device f32[2]``
-        (loss, top-1), under DPCEngine.capture_train_step's contract: cached by (static input buffer, exchange, carve-out, side_off,
-        refill identity, baked host scalars -- lr, wd, both dropouts and seeds, the Adam segment table); a replay raises once one of
-        the baked values changed; every replay is one optimizer step; the graphs are parked, never destroyed.  The labels are read
-        from ``self.target`` as they stand: drawn inside the graph by ``refill=lambda: eng.fill_synthetic(seed)``, or set eagerly
-        before each replay (set_labels).  block=None: the step starts from the stem's operand (load_recipe / fill_synthetic).
-
-        Where the backward stops (grad_wanted(): the optimizer's groups, no_grad_params) is decided HERE and is part of the key.
-        One graph without an exchange.  With the two-bucket exchange and a full backward: graph A (forward, backward down to layer2)
-        -> allreduce.start(tail) -> graph B (layer1 + stem) -> allreduce.finish(head) -> graph C (Adam), cut where DPCEngine cuts.
-        With a truncated backward (a frozen backbone) there is nothing between the two exchange points, so the capture is cut ONCE:
-        graph A (forward, head / ConvGRU backward) -> allreduce.start(tail) -> allreduce.finish(empty first bucket), as the eager
-        step does -> graph B (Adam).  No empty hipGraph is created or replayed."""
-        buf = self.x_s2d if block is None else block
-        need_backbone = self.grad_wanted()[0]
-        key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
-               id(refill) if refill is not None else None, tuple(sorted(self.no_grad_params))) + self._baked_scalars()
-        two_bucket = allreduce is not None and hasattr(allreduce, "start")
-        split = self.grad_split if need_backbone else 0   # the first bucket of the exchange: empty when the backward was truncated
-        tail, head, whole, result = self.flat_g[self.grad_split:], self.flat_g[:split], self.flat_g, self.result
-
-        def warm():
-            for _ in range(warmup):
-                self.train_step(block, None, allreduce=allreduce)
-
-        def body(cut):
-            self.forward(block, None, train=True)
-            if two_bucket and not need_backbone:   # backward() hands the tail over and returns: one cut serves both exchange points
-                self.backward(on_tail_ready=lambda _tail: None)
-                cut()
-            else:
-                self.backward(on_tail_ready=cut if two_bucket else None)
-                if allreduce is not None:
-                    cut()
-            host_steps = self._step_count
-            self.adam_step()
-            self._step_count = host_steps  # capture executes nothing
-
-        def run(eng, graphs):
-            graphs[0].replay()
-            if two_bucket:
-                allreduce.start(tail)
-                if need_backbone:
-                    graphs[1].replay()
-                allreduce.finish(head)
-                graphs[-1].replay()
-            elif allreduce is not None:
-                allreduce(whole)
-                graphs[1].replay()
-            eng._step_count += 1
-            eng.packed_for_step = -1
-            return result
-
-        return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
-                             refill, block=buf)
-
-    def capture_eval_step(self, refill=None):
-        """Captures one evaluation step on the stem's operand and the labels as they stand -- `refill`, then forward(None, None,
-        train=False) -- into one hipGraph and returns ``replay() -> device f32[2]``.  The weight repack is inside the graph, so a replay
-        evaluates the weights and running buffers of now.  Same rules as capture_train_step.  No eager warm-up: run one eager
-        eval-mode forward first (it allocates its ReLU masks on first use)."""
-        key = ("eval", self.x_s2d.data_ptr(), tuple(sorted(self.side_off)), id(refill) if refill is not None else None) + self._baked_scalars()
-        result = self.result
-
-        def warm():
-            if self._pack_table is None:
-                self.pack_weights()   # builds the static repack table: its host-to-device copy cannot be captured
-
-        def body(cut):
-            self.forward(None, None, train=False)
-
-        def run(eng, graphs):
-            graphs[0].replay()
-            return result
-
-        return self._capture(key, "evaluation", "capture_eval_step() again", warm, body, run, refill)
 
     # ---- the video-level test of eval/test.py:303-343 (csrc/lc_test.hip): per-video state, run totals and the confusion matrix on the device
     def test_reset(self):

@@ -3,7 +3,8 @@
     python -m dpc_amd.lc_main --net resnet18 --img_dim 128 --batch_size 128 --gpu 0 --pretrain <dpc checkpoint> --synthetic 20
 
 train() / validate() / test() follow eval/test.py:218-343 on the LCEngine (one process per GPU, RCCL gradient
-all-reduce as in dpc_amd.main).  Data: without ``--frames`` the input is synthetic N(0,1) video with random labels in the
+all-reduce as in dpc_amd.main: entry.launch / entry.open_rank; ``--graph`` steps go through entry.StepDriver, which replays the
+engine's capture_train_step / capture_eval_step).  Data: without ``--frames`` the input is synthetic N(0,1) video with random labels in the
 dataset's tensor layout; with
 
     python -m dpc_amd.lc_main --frames videos.npy --labels labels.npy [--lengths lengths.npy] --pretrain <dpc checkpoint> --save_dir out
@@ -55,6 +56,8 @@ import os
 import time
 
 import torch
+
+from .entry import StepDriver, average_over_ranks, launch, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -211,16 +214,7 @@ def lr_milestones(dataset: str, img_dim: int):
 
 
 def _worker(rank: int, world: int, args, port: int):
-    gpus = [int(g) for g in str(args.gpu).split(',') if g != '']
-    sim = getattr(args, '_simulator', None)   # tests only (CPU tier): the host-side SIMT simulator handle; the command line cannot set it
-    dev = torch.device('cpu') if sim is not None else torch.device('cuda', gpus[rank] if world > 1 else gpus[0])
-    if sim is None:
-        torch.cuda.set_device(dev)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist_
-        dist = dist_
-        dist.init_process_group('nccl', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world, device_id=dev)
+    dev, sim, dist = open_rank(rank, world, args, port)
     from . import checkpoint as ckpt
     from .lc import LC, LCEngine
     from .parallel import make_allreduce
@@ -259,14 +253,17 @@ def _worker(rank: int, world: int, args, port: int):
         groups = [([k for k in eng.offsets if k.startswith(('final_bn.', 'final_fc.'))], base_lr)]
         log('=> train only final_bn / final_fc on a frozen backbone + ConvGRU (batch statistics, running buffers updated)')
 
-    # --graph: per run, the first `warm[train]` steps of each kind run eagerly, then one captured step per kind is replayed.  lr / wd / the
-    # segment table are baked into a capture: set_lr drops the entry's handle, and the next step asks the engine again -- the replay that
-    # exists when nothing changed, a new capture (the old one stays parked) when the schedule passed a milestone
-    warm, captured = {True: 2, False: 1}, {True: None, False: None}
+    # --graph, synthetic input: `refill` draws batch and labels on the device in front of the step (inside the graph once it is a replay);
+    # --frames: load_recipe and set_labels fill operand and labels eagerly before each step and the graph starts from them.
+    # lr / wd / the segment table are baked into a capture: set_lr drops the driver's handles, and the next step asks the engine again
+    # -- the replay that exists when nothing changed, a new capture (the old one stays parked) when the schedule passed a milestone
+    allreduce = make_allreduce(dist, world)
+    refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
+    steps = StepDriver(eng, args.graph, allreduce, refill, refill)
 
     def set_lr(mult, saved=None):
         """the schedule scales every group; saved: the groups' lrs of a resumed checkpoint"""
-        captured[True] = captured[False] = None
+        steps.invalidate()
         eng.lr = base_lr * mult
         if groups is not None:
             lrs = saved if saved is not None else [lr * mult for _, lr in groups]
@@ -308,7 +305,6 @@ def _worker(rank: int, world: int, args, port: int):
                         raise ValueError("the checkpoint's optimizer groups are not those of --train_what %s" % args.train_what)
                     ckpt.load_optimizer_state(eng, ck['optimizer'], names=[k for ks, _ in groups for k in ks])
                     set_lr(1.0, saved=[float(g['lr']) for g in saved])
-    allreduce = make_allreduce(dist, world)
     probe = getattr(args, '_probe', None)   # tests only: the rank leaves its arenas (and in test mode the totals) behind
     src_train = src_val = None
     if args.frames:   # labelled uint8 frames in (eval/dataset_3d_lc.py + the transforms of eval/test.py:121-126,161-176 on the GPU)
@@ -359,10 +355,7 @@ def _worker(rank: int, world: int, args, port: int):
                 torch.randint(0, args.num_class, (per_gpu,), device=dev, generator=gen))
 
     def reduce(res):
-        vals = res.clone()
-        if dist is not None:
-            dist.all_reduce(vals, op=dist.ReduceOp.AVG)
-        return vals.cpu().tolist()  # one packed D2H per logged step
+        return average_over_ranks(dist, res.clone(), world).cpu().tolist()  # one packed D2H per logged step
 
     if args.test:  # eval/test.py:306-343: eval mode; softmax averaged over the clip's sequences, top-1 / top-5
         top1 = top5 = loss_sum = 0.0
@@ -379,62 +372,42 @@ def _worker(rank: int, world: int, args, port: int):
         log('Loss {:.4f}\t Acc top1: {:.4f} Acc top5: {:.4f} \t'.format(loss_sum / n, top1 / n, top5 / n))
         log('(test checkpoint epoch {})'.format(num_epoch))
     else:
-        # --graph, synthetic input: `refill` draws batch and labels on the device in front of the step (inside the graph once captured);
-        # --frames: load_recipe and set_labels fill operand and labels eagerly before each step and the graph starts from them
-        refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
-
         def step(train: bool, feed):
-            """one train / validation step, eager or replayed; returns (device f32[2], replayed)"""
+            """one train / validation step, eager or replayed; returns its device f32[2]"""
             x = y = None
             if feed is not None:
                 frames, starts, clips, y = next(feed)
                 eng.load_recipe(frames, starts, clips, ds=args.ds)   # fills the stem's operand; no f32 video in between
             elif not args.graph:
                 x, y = batch()
-            if args.graph and warm[train] == 0:
-                if y is not None:
-                    eng.set_labels(y)
-                if captured[train] is None:
-                    captured[train] = (eng.capture_train_step(None, allreduce=allreduce, warmup=0, refill=refill) if train
-                                       else eng.capture_eval_step(refill))
-                return captured[train], True
-            if args.graph:   # eager warm-up step
-                warm[train] -= 1
-                if refill is not None:
-                    refill()
-            if train:
-                return eng.train_step(x, y, allreduce=allreduce), False
-            eng.forward(x, y, train=False)
-            return eng.result, False
+
+            def eager():
+                if train:
+                    return eng.train_step(x, y, allreduce=allreduce)
+                eng.forward(x, y, train=False)
+                return eng.result
+
+            # a replay reads the labels as they stand: the feed's are set in front of it (synthetic ones are drawn inside the graph)
+            return steps.step(train, eager, (lambda: eng.set_labels(y)) if y is not None else None)[0]
 
         for epoch in range(args.start_epoch, args.epochs):
             n_train = len(src_train) if src_train is not None else args.synthetic
             feed = src_train.epoch(dev) if src_train is not None else None
-            replayed, ev0, ev1 = 0, None, None
             for idx in range(n_train):  # train(): eval/test.py:218-271
-                res, replay = step(True, feed)
-                if replay:
-                    if ev0 is None:
-                        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        ev0.record()
-                    res = res()
-                    ev1.record()
-                    replayed += 1
+                res = step(True, feed)
                 if idx % args.print_freq == 0:
                     loss, acc = reduce(res)
                     log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr),
                         flush=True)
                     iteration += 1  # advanced on logged steps only, as the reference does (eval/test.py:262-270)
-            if replayed:   # device time from the first replayed train step of the epoch to the end of its last one
-                ev1.synchronize()
-                ms = ev0.elapsed_time(ev1) / replayed
-                log('Graph replay: {0} steps, {1:.3f} ms/step, {2:.1f} clips/s'.format(replayed, ms, args.batch_size * 1e3 / ms), flush=True)
+            line = steps.replay_line(args.batch_size)
+            if line:
+                log(line, flush=True)
             vl = va = 0.0
             n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
             feed = src_val.epoch(dev) if src_val is not None else None
             for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
-                res, replay = step(False, feed)
-                loss, acc = reduce(res() if replay else res)
+                loss, acc = reduce(step(False, feed))
                 vl += loss
                 va += acc
             nv = max(n_val, 1)
@@ -462,8 +435,7 @@ def _worker(rank: int, world: int, args, port: int):
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
-    gpus = [g for g in str(args.gpu).split(',') if g != '']
-    world = max(len(gpus), 1)
+    world = world_size(args)
     if args.test and args.frames and world != 1:   # the reference's DataParallel over the windows of a video is not reproduced
         raise ValueError('--test with --frames runs on one GPU (the windows of a video are chunked on it): pass --gpu 0')
     if args.retrieval:
@@ -480,11 +452,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
             raise ValueError('--graph replays the eval-mode step: it cannot be combined with --retrieval_bn batch')
     if _simulator is not None and world != 1:
         raise ValueError('the simulator runs one rank')
-    if world == 1:
-        _worker(0, 1, args, 0)
-    else:
-        import torch.multiprocessing as mp
-        mp.spawn(_worker, args=(world, args, 29500 + (os.getpid() % 2000)), nprocs=world, join=True)
+    launch(_worker, args)
 
 
 if __name__ == '__main__':

@@ -14,7 +14,8 @@ decoded uint8 frames [clips, F, H0, W0, 3] on which the training transform of ``
 with ``--offsets``, a packed store of videos of any length) to HBM once and draws the transform on the device
 (data.ResidentFrameSource -> engine.load_resident): no host work per step; a different, equally distributed sample of clips.
 ``--graph`` runs every step after a short eager warm-up as a replay of one captured train step and one captured validation step
-(DESIGN.md §9.5.1); the synthetic input is then drawn on the device inside the graph (engine.fill_synthetic) instead of by torch.randn.
+(entry.StepDriver over the engine's capture_train_step / capture_eval_step; the rank processes are entry.launch /
+entry.open_rank, shared with dpc_amd.lc_main); the synthetic input is then drawn on the device inside the graph (engine.fill_synthetic) instead of by torch.randn.
 Checkpoints are the reference's dictionary (``module.``-prefixed state_dict incl. alias keys, torch-Adam-layout
 ``optimizer``; dpc/main.py:166-174, utils/utils.py:14-26) written and read by ``dpc_amd/checkpoint.py``: a file
 written here resumes in the reference and vice versa (tests/test_checkpoint.py).
@@ -27,6 +28,8 @@ import re
 import time
 
 import torch
+
+from .entry import StepDriver, average_over_ranks, launch, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -94,41 +97,12 @@ class AverageMeter:
         return sum(self.local) / max(len(self.local), 1)
 
 
-def average_over_ranks(dist, vals: torch.Tensor, world: int) -> torch.Tensor:
-    """mean over ranks of a small device tensor, in place (the logged loss / top-k: equal shards, so the mean of per-rank means is the
-    reference's mean over the gathered rows, dpc/main.py:211-218).  RCCL averages in the collective; gloo (CPU tier) has no AVG."""
-    if dist is None or world <= 1:
-        return vals
-    if dist.get_backend() == 'nccl':
-        dist.all_reduce(vals, op=dist.ReduceOp.AVG)
-    else:
-        dist.all_reduce(vals, op=dist.ReduceOp.SUM)
-        vals.div_(world)
-    return vals
-
-
 def _worker(rank: int, world: int, args, port: int):
-    gpus = [int(g) for g in str(args.gpu).split(',') if g != '']
     torch.manual_seed(0)  # dpc/main.py:50
-    sim = getattr(args, '_simulator', None)   # tests only (CPU tier): the host-side SIMT simulator handle; the command line cannot set it
-    if sim == 'emu':   # a spawned rank of the CPU tier loads its own handle (a ctypes library does not pickle)
-        from . import _lib
-        sim = _lib.load_emulator()
-    dev = torch.device('cpu') if sim is not None else torch.device('cuda', gpus[rank] if world > 1 else gpus[0])
     from .parallel import configure_rccl, default_reserve_cus
     if world > 1:
         configure_rccl(world)   # before this process's first HIP call: few long-lived RCCL channels beside the backward pass (parallel.py)
-    if sim is None:
-        torch.cuda.set_device(dev)
-    dist = None
-    if world > 1:
-        import torch.distributed as dist_
-        dist = dist_
-        if sim is None:
-            dist.init_process_group('nccl', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world, device_id=dev)
-        else:   # CPU tier: the same rank processes over gloo
-            torch.set_num_threads(max(1, (os.cpu_count() or 2) // (2 * world)))
-            dist.init_process_group('gloo', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world)
+    dev, sim, dist = open_rank(rank, world, args, port)
     from .engine import DPCEngine
     from .model import DPC_RNN
     from .parallel import make_allreduce
@@ -206,15 +180,18 @@ def _worker(rank: int, world: int, args, port: int):
             src_train = mk(args.frames)
             src_val = mk(args.val_frames) if args.val_frames else src_train
 
-    # --graph: per run, the first `warm[train]` steps of each kind run eagerly, then ONE captured step per kind is replayed.  Synthetic
-    # input: `refill` draws the batch on the device in front of the step (inside the graph once captured); --frames: load_recipe fills
-    # the operand eagerly before each step and the graph starts from it; --resident: `refill` advances the source's cursor, draws
-    # the recipe and gathers from the store, all on the device (engine.load_resident) -- in front of every eager step and inside the graph
-    warm, captured = {True: 2, False: 1}, {True: None, False: None}
-    refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
-    refills = {True: refill, False: refill}
+    # Where the operand of a step comes from.  Synthetic input under --graph: `refill` draws the batch on the device in front of the
+    # step (inside the graph once the step is a replay); --frames: load_recipe fills the operand eagerly before each step and the graph starts
+    # from it; --resident: `refill` advances the source's cursor, draws the recipe and gathers from the store, all on the device
+    # (engine.load_resident) -- in front of every eager step, also without --graph, and inside the graph
+    refill = refill_val = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
     if args.resident:
-        refills = {True: lambda: eng.load_resident(src_train), False: lambda: eng.load_resident(src_val)}
+        refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
+    steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
+
+    def validate(block):   # validate(): dropout off, BN still batch statistics (dpc/main.py:249-282, model_3d.py:28)
+        eng.forward(block, train=False, materialise=False)  # loss / top-k only: the score is never written (bf16)
+        return eng.loss_topk(with_grad=False)
 
     def run_epoch(train: bool, epoch: int):
         losses, accs = AverageMeter(), [AverageMeter() for _ in range(3)]
@@ -222,10 +199,8 @@ def _worker(rank: int, world: int, args, port: int):
         src = src_train if train else src_val
         n_batches = len(src) if src is not None else args.synthetic
         feed = src.epoch(dev) if src is not None and not args.resident else None
-        refill = refills[train]
         if args.resident:
             src.begin_epoch()   # the epoch's permutation to the device, the cursor to 0: the one host-to-device copy of the epoch
-        replayed, ev0, ev1 = 0, None, None
         for idx in range(n_batches):
             tic = time.time()
             block = None
@@ -234,27 +209,7 @@ def _worker(rank: int, world: int, args, port: int):
                 eng.load_recipe(frames, starts, clips, ds=src.ds)   # fills the stem's operand; no f32 video in between
             elif not args.graph and not args.resident:
                 block = torch.randn(shape, device=dev, generator=gen)
-            replay = args.graph and warm[train] == 0
-            if args.graph and not replay:   # eager warm-up step
-                warm[train] -= 1
-            if not replay and refill is not None:
-                refill()
-            if replay:
-                if captured[train] is None:
-                    captured[train] = (eng.capture_train_step(None, allreduce=allreduce, warmup=0, refill=refill) if train
-                                       else eng.capture_eval_step(refill))
-                if train and ev0 is None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                res = captured[train]()
-                if train:
-                    ev1.record()
-                    replayed += 1
-            elif train:
-                res = eng.train_step(block, allreduce=allreduce)
-            else:  # validate(): dropout off, BN still batch statistics (dpc/main.py:249-282, model_3d.py:28)
-                eng.forward(block, train=False, materialise=False)  # loss / top-k only: the score is never written (bf16)
-                res = eng.loss_topk(with_grad=False)
+            res, _ = steps.step(train, (lambda: eng.train_step(block, allreduce=allreduce)) if train else (lambda: validate(block)))
             if idx % args.print_freq == 0 or not train:
                 vals = average_over_ranks(dist, res.clone(), world)
                 loss, t1, t3, t5 = vals.cpu().tolist()  # ONE packed D2H (the reference does five .item() syncs per step)
@@ -266,11 +221,9 @@ def _worker(rank: int, world: int, args, port: int):
                         epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic), flush=True)
                 if train:
                     iteration += 1
-        if replayed:   # device time from the first replayed train step of the epoch to the end of its last one
-            ev1.synchronize()
-            ms = ev0.elapsed_time(ev1) / replayed
-            if rank == 0:
-                print('Graph replay: {0} steps, {1:.3f} ms/step, {2:.1f} clips/s'.format(replayed, ms, args.batch_size * 1e3 / ms), flush=True)
+        line = steps.replay_line(args.batch_size)
+        if line and rank == 0:
+            print(line, flush=True)
         return losses.local_avg, accs[0].local_avg, [a.local_avg for a in accs]
 
     for epoch in range(args.start_epoch, args.epochs):
@@ -302,16 +255,9 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     if args.resident and not args.frames:
         raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')
-    gpus = [g for g in str(args.gpu).split(',') if g != '']
-    world = max(len(gpus), 1)
-    if _simulator is not None and world != 1:
+    if _simulator is not None and world_size(args) != 1:
         args._simulator = 'emu'   # the rank processes (gloo instead of RCCL) load the simulator themselves
-    if world == 1:
-        _worker(0, 1, args, 0)
-    else:
-        import torch.multiprocessing as mp
-        port = 29500 + (os.getpid() % 2000)
-        mp.spawn(_worker, args=(world, args, port), nprocs=world, join=True)
+    launch(_worker, args)
 
 
 if __name__ == '__main__':
