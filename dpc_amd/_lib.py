@@ -20,7 +20,7 @@ EMU_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tests", "simt_emu", "libdpc
 
 F32, BF16 = 0, 1
 ERR_ARG, ERR_LAUNCH, ERR_UNSUPPORTED = -1, -2, -3   # DPC_ERR_* (include/dpc_hip.h)
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 
 def dtype_code(dt: torch.dtype) -> int:
@@ -78,7 +78,10 @@ class Resample(C.Structure):
 class RecipeDesc(C.Structure):
     """struct dpc_recipe_desc (include/dpc_hip.h)"""
     _fields_ = ([(n, C.c_double) for n in ("sized_p", "gray_p", "jitter_p", "brightness", "contrast", "saturation", "hue")] +
-                [("flip_code", C.c_int32), ("reserved", C.c_int32)])
+                [("flip_code", C.c_int32), ("flags", C.c_int32)])
+
+
+RECIPE_JITTER_CONSISTENT, RECIPE_SCALE_AFTER_SIZED = 1, 2   # DPC_RECIPE_* (include/dpc_hip.h): bits of RecipeDesc.flags
 
 
 def recipe_slots(n_frames: int) -> int:
@@ -172,6 +175,8 @@ _SIGS = {
                            C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _i32, _vp, _vp],
     "dpc_draw_recipe": [C.POINTER(RecipeDesc), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_uint64, _vp, _vp,
                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dpc_draw_recipe_ex": [C.POINTER(RecipeDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, C.c_uint64,
+                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "dpc_lc_test_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "dpc_lc_test_finish": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_embed_accumulate": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],

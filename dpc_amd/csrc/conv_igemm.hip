@@ -732,4 +732,4 @@ extern "C" int dpc_gemm_nt_splitk(int32_t dtype, int32_t M, int32_t N, int32_t K
     return launch_igemm<bf16_t, float>(p, bn, stream);
 }
 
-extern "C" int dpc_abi_version(void) { return 1; }
+extern "C" int dpc_abi_version(void) { return 2; }

@@ -20,6 +20,10 @@
 // clip): every clip owns DPC_RECIPE_SLOTS(N * SL) slots in the layout of include/dpc_hip.h, a rejected crop attempt keeps its
 // slots, so a draw is a pure function of (seed, counter, clip, slot).  These are NOT the draws of Python's `random`: a --resident
 // run sees a different, equally distributed sample than a --frames run.
+// dpc_draw_recipe_ex adds what the classifier's recipes (eval/test.py:161-176; dpc_amd.lc_main --resident) need, in the same slots:
+// ColorJitter(consistent=True) -- one draw, frame 0's slots, copied to every frame; the NEAREST Scale((size, size)) behind
+// RandomSizedCrop(crop) -- the sized crop works at `crop` and output row i shows row scale_tab[i] of its table; a `lengths` table for
+// a dense store whose videos are shorter than their slot; and the batch's labels gathered by video index into `target`.
 // Latency-sized like lc_test.hip: one workgroup per clip; every lane repeats the clip's few scalar decisions (nothing shared, no barrier),
 // then the lanes take the 2 * size table rows and the N * SL frames.
 #include "philox.h"
@@ -101,16 +105,21 @@ __device__ void table_row(const Axis& a, int i, int KS, const int32_t* scale_tab
 }
 
 __global__ __launch_bounds__(256) void draw_recipe_kernel(dpc_recipe_desc rc, const int32_t* video_idx, const int32_t* step_dev, const long long* offsets,
-                                                          int B, int W0, int H0, int crop, int size, int n_fr, int span_frames, int KS,
-                                                          const int32_t* scale_tab, unsigned long long seed, const int32_t* draw_dev,
-                                                          const float* uniforms, dpc_clip_aug* aug, long long* clip_first, int8_t* gray,
-                                                          dpc_frame_jitter* jitter, int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk) {
+                                                          const long long* lengths, const long long* labels, int B, int W0, int H0, int crop,
+                                                          int size, int n_fr, int span_frames, int KS, const int32_t* scale_tab,
+                                                          unsigned long long seed, const int32_t* draw_dev, const float* uniforms,
+                                                          dpc_clip_aug* aug, long long* clip_first, int8_t* gray, dpc_frame_jitter* jitter,
+                                                          int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk, long long* target) {
     const int b = blockIdx.x;
     if (b >= B) return;
     const Draw dr = {uniforms, DPC_RECIPE_SLOTS(n_fr), b, (uint32_t)draw_dev[0], (uint32_t)seed, (uint32_t)(seed >> 32)};
     const long long row = step_dev ? (long long)step_dev[0] - 1 : 0;
     const int vid = video_idx[row * B + b];
-    const long long first = offsets[vid], vlen = offsets[vid + 1] - first;
+    const long long first = offsets[vid], vlen = lengths ? lengths[vid] : offsets[vid + 1] - first;
+    // DPC_RECIPE_SCALE_AFTER_SIZED: the sized crop resizes to `crop` and the NEAREST Scale picks rows of that table; `out` is the side
+    // RandomSizedCrop / CenterCrop work at
+    const bool scale_after = (rc.flags & DPC_RECIPE_SCALE_AFTER_SIZED) != 0, consistent = (rc.flags & DPC_RECIPE_JITTER_CONSISTENT) != 0;
+    const int out = scale_after ? crop : size;
 
     // ---- the clip's scalar decisions (every lane: a few dozen flops, cheaper than a broadcast through LDS)
     const int start = (int)floor(dr.u(SLOT_START) * (double)(vlen - span_frames));   // idx_sampler: uniform on [0, vlen - N*SL*ds)
@@ -126,30 +135,30 @@ __global__ __launch_bounds__(256) void draw_recipe_kernel(dpc_recipe_desc rc, co
         bool found = false;
         for (int a = 0; a < ATTEMPTS && !found; ++a) {
             const int s = SLOT_ATTEMPT + ATTEMPT_SLOTS * a;
-            const double target = dr.uniform(s, 0.5, 1.0) * (double)(W0 * H0);
+            const double target_area = dr.uniform(s, 0.5, 1.0) * (double)(W0 * H0);
             const double aspect = dr.uniform(s + 1, 3. / 4, 4. / 3);
-            int w = (int)rint(sqrt_rn(target * aspect));
-            int h = (int)rint(sqrt_rn(target / aspect));
+            int w = (int)rint(sqrt_rn(target_area * aspect));
+            int h = (int)rint(sqrt_rn(target_area / aspect));
             if (dr.u(s + 2) < 0.5) { const int t = w; w = h; h = t; }
             if (w <= W0 && h <= H0) {
                 x1 = dr.randint(s + 3, W0 - w);
                 y1 = dr.randint(s + 4, H0 - h);
-                ax = {RESAMPLE, w, size, 0};
-                ay = {RESAMPLE, h, size, 0};
+                ax = {RESAMPLE, w, out, 0};
+                ay = {RESAMPLE, h, out, 0};
                 found = true;
             }
         }
         if (!found) {
             int ow, oh;
-            if (W0 < H0) { ow = size; oh = (int)((double)(size * H0) / (double)W0); }
-            else { oh = size; ow = (int)((double)(size * W0) / (double)H0); }
-            ax = {RESAMPLE, W0, ow, (int)rint((double)(ow - size) / 2.)};
-            ay = {RESAMPLE, H0, oh, (int)rint((double)(oh - size) / 2.)};
+            if (W0 < H0) { ow = out; oh = (int)((double)(out * H0) / (double)W0); }
+            else { oh = out; ow = (int)((double)(out * W0) / (double)H0); }
+            ax = {RESAMPLE, W0, ow, (int)rint((double)(ow - out) / 2.)};
+            ay = {RESAMPLE, H0, oh, (int)rint((double)(oh - out) / 2.)};
         }
-    } else {   // the failed `p` draw: CenterCrop(size)
-        x1 = (int)rint((double)(W0 - size) / 2.);
-        y1 = (int)rint((double)(H0 - size) / 2.);
-        ax.mode = ay.mode = IDENTITY;
+    } else {   // the failed `p` draw: CenterCrop(out); behind it the NEAREST Scale is the index map of the SCALE mode
+        x1 = (int)rint((double)(W0 - out) / 2.);
+        y1 = (int)rint((double)(H0 - out) / 2.);
+        if (!scale_after) ax.mode = ay.mode = IDENTITY;
     }
     const bool jit_on = rc.jitter_p >= 0.0 && dr.u(SLOT_JITTER_P) < rc.jitter_p;
 
@@ -158,12 +167,15 @@ __global__ __launch_bounds__(256) void draw_recipe_kernel(dpc_recipe_desc rc, co
         a.start = start; a.x1 = x1; a.y1 = y1; a.flip = flip;
         aug[b] = a;
         clip_first[b] = first;
+        if (target) target[b] = labels[vid];
     }
     for (int r = threadIdx.x; r < 2 * size; r += blockDim.x) {
         const bool isx = r < size;
         const int i = isx ? r : r - size;
         const long long o = (long long)b * size + i;
-        table_row(isx ? ax : ay, i, KS, scale_tab, (isx ? xb : yb) + o * 2, (isx ? xk : yk) + o * KS);
+        const Axis& a = isx ? ax : ay;
+        const int t = (scale_after && a.mode == RESAMPLE && scale_tab) ? scale_tab[i] : i;   // the row of the `crop` table output row i shows
+        table_row(a, t, KS, scale_tab, (isx ? xb : yb) + o * 2, (isx ? xk : yk) + o * KS);
     }
     for (int f = threadIdx.x; f < n_fr; f += blockDim.x) {
         const int s = SLOT_FRAME + FRAME_SLOTS * f;
@@ -174,22 +186,23 @@ __global__ __launch_bounds__(256) void draw_recipe_kernel(dpc_recipe_desc rc, co
         j.factor[0] = j.factor[1] = j.factor[2] = 0.f;
         j.hue_shift = 0;
         j.order[0] = j.order[1] = j.order[2] = j.order[3] = 255;
+        const int sj = consistent ? SLOT_FRAME : s;   // consistent=True: ONE get_params draw, frame 0's slots, copied to every frame
         if (jit_on) {   // ColorJitter.get_params: four uniforms, then random.shuffle of the steps whose range is not 0
             const double v[4] = {rc.brightness, rc.contrast, rc.saturation, rc.hue};
             int n = 0;
             for (int op = 0; op < 4; ++op) {
                 if (v[op] == 0.0) continue;
                 if (op == 3) {
-                    const double fh = dr.uniform(s + 2 + op, -v[op], v[op]);
+                    const double fh = dr.uniform(sj + 2 + op, -v[op], v[op]);
                     j.hue_shift = (int)(fh * 255.0) & 0xFF;   // np.uint8(hue_factor * 255): C truncation, uint8 wrap
                 } else {
                     const double lo = 1.0 - v[op] > 0.0 ? 1.0 - v[op] : 0.0;
-                    j.factor[op] = (float)dr.uniform(s + 2 + op, lo, 1.0 + v[op]);
+                    j.factor[op] = (float)dr.uniform(sj + 2 + op, lo, 1.0 + v[op]);
                 }
                 j.order[n++] = (uint8_t)op;
             }
             for (int i = n - 1; i >= 1; --i) {   // Fisher-Yates from the top, as random.shuffle walks
-                const int q = (int)floor(dr.u(s + 6 + (3 - i)) * (double)(i + 1));
+                const int q = (int)floor(dr.u(sj + 6 + (3 - i)) * (double)(i + 1));
                 const uint8_t t = j.order[i]; j.order[i] = j.order[q]; j.order[q] = t;
             }
         }
@@ -199,26 +212,46 @@ __global__ __launch_bounds__(256) void draw_recipe_kernel(dpc_recipe_desc rc, co
 
 }  // namespace
 
+extern "C" int dpc_draw_recipe_ex(const dpc_recipe_desc* rc, const int32_t* video_idx, const int32_t* step_dev, const int64_t* offsets,
+                                  const int64_t* lengths, const int64_t* labels, int32_t B, int32_t W0, int32_t H0, int32_t crop, int32_t size,
+                                  int32_t N, int32_t SL, int32_t ds, int32_t KS, const int32_t* scale_tab, uint64_t seed, const int32_t* draw_dev,
+                                  const float* uniforms, dpc_clip_aug* aug, int64_t* clip_first, int8_t* gray, dpc_frame_jitter* jitter,
+                                  int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk, int64_t* target, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!rc || !video_idx || !offsets || !draw_dev || !aug || !clip_first || !gray || !jitter || !xb || !xk || !yb || !yk) return DPC_ERR_ARG;
+    if ((labels == nullptr) != (target == nullptr)) return DPC_ERR_ARG;   // the label gather: both tables or neither
+    if (B <= 0 || W0 <= 0 || H0 <= 0 || size <= 0 || N <= 0 || SL <= 0 || ds <= 0 || KS <= 0) return DPC_ERR_ARG;
+    if (B > 1024 || size > 1024 || (long long)W0 * H0 >= (1ll << 30) || (long long)N * SL * ds >= (1ll << 30)) return DPC_ERR_UNSUPPORTED;
+    if (rc->flags & ~(DPC_RECIPE_JITTER_CONSISTENT | DPC_RECIPE_SCALE_AFTER_SIZED)) return DPC_ERR_ARG;
+    if (rc->sized_p > 1.0 || rc->gray_p > 1.0 || rc->jitter_p > 1.0 || rc->flip_code < 0 || rc->flip_code > 2) return DPC_ERR_ARG;
+    if (rc->brightness < 0.0 || rc->contrast < 0.0 || rc->saturation < 0.0 || rc->hue < 0.0 || rc->hue > 0.5) return DPC_ERR_ARG;
+    const bool scale_after = (rc->flags & DPC_RECIPE_SCALE_AFTER_SIZED) != 0;
+    if (rc->sized_p < 0.0) {   // RandomCrop(crop) (+ NEAREST Scale): the box must fit the frame; one tap per row
+        if (scale_after) return DPC_ERR_ARG;   // the flag is about the Scale behind RandomSizedCrop
+        if (crop <= 0 || crop > W0 || crop > H0 || (!scale_tab && crop != size)) return DPC_ERR_ARG;
+    } else {
+        const int m = W0 > H0 ? W0 : H0;
+        const int out = scale_after ? crop : size;   // the side RandomSizedCrop resizes to
+        if (scale_after && (crop <= 0 || (scale_tab != nullptr) != (crop != size))) return DPC_ERR_ARG;   // the table iff there is a Scale
+        if (scale_after && crop > 1024) return DPC_ERR_UNSUPPORTED;                   // as `size`: out * max(W0, H0) stays inside an int
+        if (KS < 2 * ((m + out - 1) / out) + 1) return DPC_ERR_ARG;                 // the widest window any accepted box can need
+        if (rc->sized_p < 1.0 && (out > W0 || out > H0)) return DPC_ERR_UNSUPPORTED;   // CenterCrop(out) would leave the frame
+    }
+    DPC_LAUNCH(draw_recipe_kernel, dim3((unsigned)B), dim3(256), stream, *rc, video_idx, step_dev, (const long long*)offsets,
+               (const long long*)lengths, (const long long*)labels, B, W0, H0, crop, size, N * SL, N * SL * ds, KS, scale_tab,
+               (unsigned long long)seed, draw_dev, uniforms, aug, (long long*)clip_first, gray, jitter, xb, xk, yb, yk, (long long*)target);
+    return dpc_launch_status();
+}
+
+// the entry of ABI 1: the same launch with the additions off (whatever the descriptor's last word holds, as before)
 extern "C" int dpc_draw_recipe(const dpc_recipe_desc* rc, const int32_t* video_idx, const int32_t* step_dev, const int64_t* offsets,
                                int32_t B, int32_t W0, int32_t H0, int32_t crop, int32_t size, int32_t N, int32_t SL, int32_t ds, int32_t KS,
                                const int32_t* scale_tab, uint64_t seed, const int32_t* draw_dev, const float* uniforms, dpc_clip_aug* aug,
                                int64_t* clip_first, int8_t* gray, dpc_frame_jitter* jitter, int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk,
-                               dpc_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!rc || !video_idx || !offsets || !draw_dev || !aug || !clip_first || !gray || !jitter || !xb || !xk || !yb || !yk) return DPC_ERR_ARG;
-    if (B <= 0 || W0 <= 0 || H0 <= 0 || size <= 0 || N <= 0 || SL <= 0 || ds <= 0 || KS <= 0) return DPC_ERR_ARG;
-    if (B > 1024 || size > 1024 || (long long)W0 * H0 >= (1ll << 30) || (long long)N * SL * ds >= (1ll << 30)) return DPC_ERR_UNSUPPORTED;
-    if (rc->sized_p > 1.0 || rc->gray_p > 1.0 || rc->jitter_p > 1.0 || rc->flip_code < 0 || rc->flip_code > 2) return DPC_ERR_ARG;
-    if (rc->brightness < 0.0 || rc->contrast < 0.0 || rc->saturation < 0.0 || rc->hue < 0.0 || rc->hue > 0.5) return DPC_ERR_ARG;
-    if (rc->sized_p < 0.0) {   // RandomCrop(crop) (+ NEAREST Scale): the box must fit the frame; one tap per row
-        if (crop <= 0 || crop > W0 || crop > H0 || (!scale_tab && crop != size)) return DPC_ERR_ARG;
-    } else {
-        const int m = W0 > H0 ? W0 : H0;
-        if (KS < 2 * ((m + size - 1) / size) + 1) return DPC_ERR_ARG;                 // the widest window any accepted box can need
-        if (rc->sized_p < 1.0 && (size > W0 || size > H0)) return DPC_ERR_UNSUPPORTED;   // CenterCrop(size) would leave the frame
-    }
-    DPC_LAUNCH(draw_recipe_kernel, dim3((unsigned)B), dim3(256), stream, *rc, video_idx, step_dev, (const long long*)offsets, B, W0, H0, crop, size,
-               N * SL, N * SL * ds, KS, scale_tab, (unsigned long long)seed, draw_dev, uniforms, aug, (long long*)clip_first, gray, jitter, xb, xk, yb,
-               yk);
-    return dpc_launch_status();
+                               dpc_stream_t stream) {
+    if (!rc) return DPC_ERR_ARG;
+    dpc_recipe_desc plain = *rc;
+    plain.flags = 0;
+    return dpc_draw_recipe_ex(&plain, video_idx, step_dev, offsets, nullptr, nullptr, B, W0, H0, crop, size, N, SL, ds, KS, scale_tab, seed,
+                              draw_dev, uniforms, aug, clip_first, gray, jitter, xb, xk, yb, yk, nullptr, stream);
 }

@@ -352,8 +352,13 @@ RECIPES = {   # dpc/main.py:114-132 as the fields of dpc_recipe_desc (include/dp
     "k400": dict(sized_p=1.0, flip_code=1, gray_p=0.5, jitter=_JITTER),
     "ucf101": dict(sized_p=None, flip_code=2, gray_p=0.5, jitter=_JITTER),
 }
-# The descriptor does not preclude the fine-tuning recipes (LC_RECIPES: sized_p 1.0 / 0.3 / 0.0, no gray, jitter p 0.3); what they
-# need beyond it is ColorJitter(consistent=True) (one draw copied to every frame) and the NEAREST Scale behind the sized crop.
+# The fine-tuning recipes (LC_RECIPES 'train' / 'val', eval/test.py:161-176) as descriptors: what they need beyond the pre-training
+# ones are the two flags of dpc_draw_recipe_ex -- ColorJitter(consistent=True) (one draw, frame 0's slots, copied to every frame)
+# and the NEAREST Scale((size, size)) behind the BILINEAR RandomSizedCrop(crop).  The test recipe draws nothing and needs no kernel.
+RESIDENT_LC_RECIPES = {
+    name: dict(sized_p=r["p"], flip_code=1, gray_p=None, jitter=r["jitter"], jitter_consistent=True, scale_after_sized=True)
+    for name, r in LC_RECIPES.items() if name != "test"
+}
 SLOT_START, SLOT_FLIP, SLOT_SIZED_P, SLOT_CROP_X, SLOT_CROP_Y, SLOT_JITTER_P, SLOT_ATTEMPT, SLOT_FRAME = 0, 1, 2, 3, 4, 5, 8, 58
 ATTEMPT_SLOTS, FRAME_SLOTS = 5, 9   # include/dpc_hip.h (dpc_draw_recipe) documents the layout
 recipe_slots = L.recipe_slots
@@ -365,13 +370,19 @@ def recipe_desc(recipe) -> "L.RecipeDesc":
     neg = lambda v: -1.0 if v is None else float(v)   # noqa: E731
     return L.RecipeDesc(neg(r.get("sized_p")), neg(r.get("gray_p")), float(j.get("p", 1.0)) if r.get("jitter") else -1.0,
                         float(j.get("brightness", 0)), float(j.get("contrast", 0)), float(j.get("saturation", 0)), float(j.get("hue", 0)),
-                        int(r.get("flip_code", 0)), 0)
+                        int(r.get("flip_code", 0)), (L.RECIPE_JITTER_CONSISTENT if r.get("jitter_consistent") else 0) |
+                        (L.RECIPE_SCALE_AFTER_SIZED if r.get("scale_after_sized") else 0))
 
 
-def resident_ks(recipe, W0: int, H0: int, size: int) -> int:
+def resident_ks(recipe, W0: int, H0: int, size: int, crop: Optional[int] = None) -> int:
     """pitch of the coefficient tables dpc_draw_recipe writes: the widest window any crop box of a W0 x H0 frame can need,
-    2 ceil(max(W0, H0) / size) + 1 (resample_tables: ksize = 2 ceil(in / out) + 1 with in <= max(W0, H0)); an index map has one tap"""
+    2 ceil(max(W0, H0) / size) + 1 (resample_tables: ksize = 2 ceil(in / out) + 1 with in <= max(W0, H0)); an index map has one tap.
+    A recipe with ``scale_after_sized`` resizes to `crop`, not to `size`: the same rule with `crop`"""
     r = RECIPES[recipe] if isinstance(recipe, str) else recipe
+    if r.get("scale_after_sized"):
+        if crop is None:
+            raise ValueError("a recipe with scale_after_sized resizes to `crop`: pass it")
+        size = crop
     return 1 if r.get("sized_p") is None else 2 * -(-max(W0, H0) // size) + 1
 
 
@@ -381,8 +392,17 @@ def recipe_from_uniforms(recipe, u, vlen: int, W0: int, H0: int, crop: int, size
     (span = num_seq * seq_len * ds; the start is uniform on [0, vlen - span)).  randint(0, n) = floor(u (n + 1)), uniform(a, b) =
     a + (b - a) u, a rejected crop attempt keeps its slots: a pure function of the row, whichever branch is taken.  Returns the dict
     ``draw_k400`` returns plus ``start``.  csrc/recipe_draw.hip makes the same decisions with the same double arithmetic on the
-    device (bit for bit, tests/resident_cases.py); fed to ``recipe_to_input`` it gives a --frames run the recipes of a --resident run."""
+    device (bit for bit, tests/resident_cases.py); fed to ``recipe_to_input`` it gives a --frames run the recipes of a --resident run.
+    The two recipe keys of the classifier's recipes (RESIDENT_LC_RECIPES; tests/resident_lc_cases.py anchors them to ``draw_lc``):
+    ``scale_after_sized``: RandomSizedCrop works at `crop` and the NEAREST Scale((size, size)) behind it picks rows
+    ``nearest_tables(crop, size)`` of its tables; ``jitter_consistent``: one get_params draw, frame 0's slots, copied to every frame."""
     r = RECIPES[recipe] if isinstance(recipe, str) else recipe
+    scale_after, consistent = bool(r.get("scale_after_sized")), bool(r.get("jitter_consistent"))
+    if scale_after and r.get("sized_p") is None:
+        raise ValueError("scale_after_sized is the Scale behind RandomSizedCrop: the recipe has none (sized_p is None)")
+    pick, out_size = None, size
+    if scale_after:                                             # everything up to the Scale happens at `crop`
+        pick, size = (nearest_tables(crop, size) if crop != size else None), crop
     u = [float(v) for v in u]
     if len(u) != recipe_slots(n_frames):
         raise ValueError(f"{recipe_slots(n_frames)} uniforms per clip of {n_frames} frames, got {len(u)}")
@@ -428,6 +448,9 @@ def recipe_from_uniforms(recipe, u, vlen: int, W0: int, H0: int, crop: int, size
             raise ValueError(f"CenterCrop({size}) of {W0} x {H0} frames leaves the frame (PIL would pad with black; not reproduced)")
         x1, y1 = int(round((W0 - size) / 2.)), int(round((H0 - size) / 2.))
         xt, yt = _tables_from_index(ident), _tables_from_index(ident)
+    if pick is not None:                                        # NEAREST Scale: a sub-sampled output is an exact subset of the rows
+        xt, yt = (xt[0][pick], xt[1][pick]), (yt[0][pick], yt[1][pick])
+    size = out_size
     gray = np.full(n_frames, -1, np.int8)
     jit = (FrameJitter * n_frames)()
     jitter, gray_p = r.get("jitter"), r.get("gray_p")
@@ -436,6 +459,8 @@ def recipe_from_uniforms(recipe, u, vlen: int, W0: int, H0: int, crop: int, size
         s = SLOT_FRAME + FRAME_SLOTS * f
         if gray_p is not None and u[s] < gray_p:
             gray[f] = int(math.floor(u[s + 1] * 3))
+        if consistent:
+            s = SLOT_FRAME                                      # ColorJitter(consistent=True): every frame repeats frame 0's draw
         j = jit[f]
         j.order[:] = [255, 255, 255, 255]
         if not jit_on:
@@ -476,13 +501,26 @@ class FrameStore:
     """Decoded videos of ANY length packed back to back: frames uint8 [total_frames, H0, W0, 3] and offsets int64 [videos + 1]
     (non-decreasing, offsets[0] == 0, offsets[-1] == total_frames), video v = frames[offsets[v]:offsets[v + 1]].  Built from such a
     packed array with its offsets (``--frames packed.npy --offsets offsets.npy``) or from the dense [clips, F, H0, W0, 3] array of
-    ``FrameSource`` (every video F frames, offsets = arange(clips + 1) * F).  ``to_device`` uploads it ONCE; after that a training
-    step reads its frames from HBM (dpc_store_to_input) and nothing crosses the host per step."""
+    ``FrameSource`` (every video F frames, offsets = arange(clips + 1) * F).  With the dense array ``lengths`` integer [clips] gives
+    the real frame count of each video (<= F, the ``--lengths`` of dpc_amd.lc_main): a video then fills only the head of its slot.
+    ``to_device`` uploads it ONCE; after that a training step reads its frames from HBM (dpc_store_to_input) and nothing crosses
+    the host per step."""
 
-    def __init__(self, frames, offsets=None):
+    def __init__(self, frames, offsets=None, lengths=None):
         fr = _load(frames, mmap=True)
         if getattr(fr, "dtype", None) != np.uint8 or fr.ndim not in (4, 5) or fr.shape[-1] != 3:
             raise ValueError("--frames wants a uint8 array [clips, F, H0, W0, 3], or with --offsets a packed [total_frames, H0, W0, 3]")
+        if lengths is not None and (offsets is not None or fr.ndim != 5):
+            raise ValueError("--lengths goes with the dense 5-D --frames array [clips, F, H0, W0, 3]; with --offsets a packed store says "
+                             "how long each video is: pass --lengths or --offsets, not both")
+        self.lengths = None
+        if lengths is not None:
+            ln = np.asarray(_load(lengths))
+            if ln.ndim != 1 or ln.shape[0] != fr.shape[0] or not np.issubdtype(ln.dtype, np.integer):
+                raise ValueError(f"--lengths wants one integer per clip: {fr.shape[0]} clips, array of shape {ln.shape} and type {ln.dtype}")
+            if ln.size and (int(ln.min()) < 0 or int(ln.max()) > fr.shape[1]):
+                raise ValueError(f"lengths must lie in [0, {fr.shape[1]}] (the frames the array holds): found {int(ln.min())} .. {int(ln.max())}")
+            self.lengths = ln.astype(np.int64)
         if fr.ndim == 5:
             if offsets is not None:
                 raise ValueError("--offsets goes with a packed 4-D array [total_frames, H0, W0, 3]; this --frames array is the dense 5-D one")
@@ -502,9 +540,15 @@ class FrameStore:
         self.H0, self.W0 = int(fr.shape[1]), int(fr.shape[2])
         self.dev: Optional[torch.Tensor] = None
         self.offsets_dev: Optional[torch.Tensor] = None
+        self.lengths_dev: Optional[torch.Tensor] = None
 
     def __len__(self):
         return self.offsets.shape[0] - 1
+
+    @property
+    def video_lengths(self) -> np.ndarray:
+        """frames of each video: ``lengths`` when given, else what the offsets leave"""
+        return self.lengths if self.lengths is not None else np.diff(self.offsets)
 
     @property
     def total_frames(self) -> int:
@@ -516,7 +560,7 @@ class FrameStore:
 
     def long_enough(self, span: int) -> np.ndarray:
         """videos with vlen - span > 0, span = num_seq * seq_len * ds (dpc/dataset_3d.py:80-82 drops the others)"""
-        return np.nonzero(np.diff(self.offsets) - span > 0)[0]
+        return np.nonzero(self.video_lengths - span > 0)[0]
 
     def to_device(self, device, reserve: int = 0, chunk_bytes: int = 64 << 20):
         """one upload, in chunks through ONE pinned staging buffer (no second host copy of the store).  `reserve` = bytes the engine
@@ -539,6 +583,7 @@ class FrameStore:
             host[:m] = src[o:o + m]
             flat[o:o + m].copy_(stage[:m])   # blocking: the staging buffer is free again when it returns
         self.dev, self.offsets_dev = dev, torch.from_numpy(self.offsets).to(device)
+        self.lengths_dev = torch.from_numpy(self.lengths).to(device) if self.lengths is not None else None
         return self
 
 
@@ -557,15 +602,29 @@ class ResidentFrameSource:
                  world: int = 1, crop: int = 224, seed: int = 0):
         if dataset not in RECIPES:
             raise ValueError("dataset not supported")   # dpc/main.py:301
+        # dpc/main.py:294, :299: k400 samples every 5th frame; dpc/main.py:117: only the ucf101 recipe crops before it scales
+        self._fields(store, dataset, num_seq, seq_len, 5 if dataset == "k400" else ds, size, batch, device, rank, world,
+                     crop if dataset == "ucf101" else size, seed)
+        if dataset == "ucf101" and (store.H0 < crop or store.W0 < crop):
+            raise ValueError(f"the ucf101 recipe crops {crop} x {crop} (dpc/main.py:117): frames of {store.W0} x {store.H0} are too small")
+        self._tables(dataset)
+
+    def _fields(self, store, dataset, num_seq, seq_len, ds, size, batch, device, rank, world, crop, seed):
+        """what every resident source is made of (the one place its fields are set); `device` must be where the store lives"""
         if store.dev is None:
             raise ValueError("upload the store first (FrameStore.to_device)")
+        if torch.device(device).type != store.dev.device.type:
+            raise ValueError(f"the store lives on {store.dev.device}, the source was asked for {device}")
         self.store, self.dataset, self.N, self.SL, self.size, self.batch, self.rank, self.world = store, dataset, num_seq, seq_len, size, batch, rank, world
-        self.ds = 5 if dataset == "k400" else ds           # dpc/main.py:294, :299
-        self.n_fr = num_seq * seq_len
-        self.crop, self.seed = (crop if dataset == "ucf101" else size), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.ds, self.n_fr, self.crop, self.seed = ds, num_seq * seq_len, crop, int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.device = store.dev.device
+        self.labels_dev: Optional[torch.Tensor] = None
+
+    def _tables(self, recipe):
+        """drop the videos too short for one clip, then this source's device tables: the epoch's video indices, the two counters and
+        what dpc_draw_recipe writes for one batch"""
+        store, num_seq, seq_len, batch, world, size = self.store, self.N, self.SL, self.batch, self.world, self.size
         H0, W0 = store.H0, store.W0
-        if dataset == "ucf101" and (H0 < crop or W0 < crop):
-            raise ValueError(f"the ucf101 recipe crops {crop} x {crop} (dpc/main.py:117): frames of {W0} x {H0} are too small")
         self.keep = store.long_enough(self.n_fr * self.ds)
         self.skipped = len(store) - len(self.keep)
         if len(self.keep) == 0:
@@ -573,10 +632,10 @@ class ResidentFrameSource:
                              "(dpc/dataset_3d.py:80-82 drops such videos)")
         if len(self) == 0:
             raise ValueError(f"{len(self.keep)} videos do not fill one batch of {batch} x {world}")
-        dev = self.device = store.dev.device
+        dev = self.device
         B, n_fr = batch, self.n_fr
-        self.desc = recipe_desc(dataset)
-        self.KS = resident_ks(dataset, W0, H0, size)
+        self.desc = recipe_desc(recipe)
+        self.KS = resident_ks(recipe, W0, H0, size, self.crop)
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)   # noqa: E731
         self.perm, self.cursor, self.draw = z(len(self) * B, torch.int32), z(1, torch.int32), z(1, torch.int32)
         self.aug, self.clip_first, self.gray = z((B, 4), torch.int32), z(B, torch.int64), z((B, n_fr), torch.int8)
@@ -603,15 +662,66 @@ class ResidentFrameSource:
         self.cursor.zero_()
         return mine
 
-    def draw_recipe(self, lib: L.Lib, uniforms: Optional[torch.Tensor] = None, video_idx: Optional[torch.Tensor] = None, call=None):
-        """dpc_draw_recipe into this source's tables for the batch the cursor points at (video_idx given: that batch, cursor unused)"""
+    def draw_recipe(self, lib: L.Lib, uniforms: Optional[torch.Tensor] = None, video_idx: Optional[torch.Tensor] = None, call=None,
+                    target: Optional[torch.Tensor] = None):
+        """dpc_draw_recipe into this source's tables for the batch the cursor points at (video_idx given: that batch, cursor unused).
+        A store with ``lengths`` or a source with labels goes through dpc_draw_recipe_ex: the same launch reads each video's length
+        from the device table and writes ``target[b] = labels[video of clip b]`` (int64 [B]; None: the labels are not gathered)"""
         st = self.store
-        args = (C.byref(self.desc), self.perm if video_idx is None else video_idx, self.cursor if video_idx is None else None, st.offsets_dev,
-                self.batch, st.W0, st.H0, self.crop, self.size, self.N, self.SL, self.ds, self.KS, self.scale_tab, self.seed, self.draw,
+        head = (C.byref(self.desc), self.perm if video_idx is None else video_idx, self.cursor if video_idx is None else None, st.offsets_dev)
+        tail = (self.batch, st.W0, st.H0, self.crop, self.size, self.N, self.SL, self.ds, self.KS, self.scale_tab, self.seed, self.draw,
                 uniforms, self.aug, self.clip_first, self.gray, self.jitter, self.xb, self.xk, self.yb, self.yk)
+        if target is not None and (self.labels_dev is None or target.dtype != torch.int64 or tuple(target.shape) != (self.batch,)
+                                   or target.device != self.device or not target.is_contiguous()):
+            raise ValueError(f"target: a contiguous int64 [{self.batch}] on {self.device}, for a source that carries labels")
+        if st.lengths_dev is None and self.labels_dev is None:
+            name, args = "dpc_draw_recipe", head + tail
+        else:
+            name, args = "dpc_draw_recipe_ex", head + (st.lengths_dev, self.labels_dev if target is not None else None) + tail + (target,)
         if call is not None:
-            return call("dpc_draw_recipe", *args)
-        return lib.call("dpc_draw_recipe", *args, lib.stream())
+            return call(name, *args)
+        return lib.call(name, *args, lib.stream())
+
+
+class ResidentLabelledSource(ResidentFrameSource):
+    """``LabelledFrameSource`` for a store that lives in HBM (``python -m dpc_amd.lc_main --frames ... --labels ... --resident``):
+    the fine-tuning recipes of eval/test.py:161-176 as RESIDENT_LC_RECIPES, drawn on the device like the pre-training ones
+    (``ResidentFrameSource``; the same Philox stream and slots, so again NOT the draws of Python's ``random``: a different, equally
+    distributed sample than ``LabelledFrameSource`` makes), and the labels, uploaded once, gathered by the draw's own launch into
+    the engine's ``target``.  recipe 'test' draws nothing: ``videos()`` walks the store in file order for the video-level protocols
+    and hands out DEVICE slices of it, so no video is uploaded again."""
+
+    def __init__(self, store: FrameStore, labels, dataset: str, num_seq: int, seq_len: int, ds: int, size: int, batch: int, num_class: int,
+                 device, recipe: str = "train", rank: int = 0, world: int = 1, crop: int = 224, seed: int = 0):
+        if dataset not in ("ucf101", "hmdb51"):
+            raise ValueError("dataset not supported")   # eval/test.py:378
+        if recipe not in LC_RECIPES:
+            raise ValueError(f"recipe must be one of {sorted(LC_RECIPES)}")
+        self._fields(store, dataset, num_seq, seq_len, ds, size, batch, device, rank, world, crop, seed)
+        labels = np.asarray(_load(labels))
+        if labels.ndim != 1 or labels.shape[0] != len(store) or not np.issubdtype(labels.dtype, np.integer):
+            raise ValueError(f"--labels wants one integer per clip: {len(store)} clips, array of shape {labels.shape} and type {labels.dtype}")
+        if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= num_class):
+            raise ValueError(f"labels must lie in [0, {num_class}): found {int(labels.min())} .. {int(labels.max())}")
+        if store.H0 < crop or store.W0 < crop:
+            raise ValueError(f"the recipes crop {crop} x {crop} (eval/test.py:122,162,170): frames of {store.W0} x {store.H0} are too small")
+        self.recipe, self.num_class, self.labels = recipe, num_class, labels.astype(np.int64)
+        self.labels_dev = torch.from_numpy(self.labels).to(self.device)
+        if recipe == "test":   # no batches, no draws: the file order of videos()
+            self.keep = store.long_enough(self.n_fr * ds)
+            self.skipped = len(store) - len(self.keep)
+        else:
+            self._tables(RESIDENT_LC_RECIPES[recipe])
+
+    def videos(self):
+        """``LabelledFrameSource.videos`` without the upload: (index, frames u8 [vlen, H0, W0, 3] -- a slice of the store ON THE DEVICE
+        --, label, window starts, the test recipe's draw) for every video long enough"""
+        st = self.store
+        lengths = st.video_lengths
+        for ci in self.keep.tolist():
+            first, vlen = int(st.offsets[ci]), int(lengths[ci])
+            starts = lc_test_windows(vlen, self.N, self.SL, self.ds, self.dataset)
+            yield ci, st.dev[first:first + vlen], int(self.labels[ci]), starts, draw_lc(st.W0, st.H0, self.crop, self.size, self.n_fr, "test")
 
 
 def store_to_input(lib: L.Lib, store: torch.Tensor, aug: torch.Tensor, clip_first: torch.Tensor, gray: Optional[torch.Tensor], rs,

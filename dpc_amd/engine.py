@@ -961,7 +961,8 @@ class BackboneEngine:
         recipe on the device (dpc_draw_recipe), gather from the store into the stem's operand (dpc_store_to_input).  Six launches
         (two counters, the draw, the gather's three; its one without ColorJitter); no host synchronisation, no host-to-device copy, no allocation after the
         first call, no address that changes: graph-safe as the `refill` of capture_train_step / capture_eval_step, and one capture
-        serves every epoch.  Follow with forward(None, ...) / train_step(None, ...)."""
+        serves every epoch.  A source with labels (data.ResidentLabelledSource) has them gathered into ``self.target`` by the draw's
+        launch (dpc_draw_recipe_ex): no set_labels, no further launch.  Follow with forward(None, ...) / train_step(None, ...)."""
         from .data import store_to_input
         if source.batch != self.B or source.N != self.N or source.SL != self.SL or source.size != self.size or source.device != self.device:
             raise ValueError("the source was built for another batch / clip shape / device than this engine")
@@ -972,7 +973,12 @@ class BackboneEngine:
         u8, ls = self._resident_ws if source.has_jitter else (None, None)
         self.call("dpc_counter_advance", source.cursor)
         self.call("dpc_counter_advance", source.draw)
-        source.draw_recipe(self.lib, call=self.call)
+        target = None
+        if source.labels_dev is not None:   # data.ResidentLabelledSource: the draw's launch gathers the batch's labels as well
+            target = getattr(self, "target", None)
+            if target is None:
+                raise ValueError("the source carries labels but this engine has no `target` to receive them (LCEngine has)")
+        source.draw_recipe(self.lib, call=self.call, target=target)
         store_to_input(self.lib, source.store.dev, source.aug, source.clip_first, source.gray, source.rs,
                        source.jitter if source.has_jitter else None, self.N, self.SL, source.ds, self.size, None, self.x_s2d, u8, ls,
                        call=self.call)

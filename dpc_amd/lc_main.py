@@ -20,6 +20,15 @@ logits averaged for the loss and the confusion matrix -- reduced on the device (
 video.  It prints the reference's result line, writes ``<ckpt>.confusion.npy`` (int64 [num_class, num_class], [pred][target])
 where the reference draws ``<ckpt>.svg`` and appends the reference's paragraph to ``test_log.md`` beside the checkpoint.  Video
 decoding, csv split files and tensorboard stay outside this build's scope: whatever produces these arrays plugs in.
+
+    python -m dpc_amd.lc_main --frames videos.npy --labels labels.npy [--lengths lengths.npy | --offsets offsets.npy] --resident [--graph] ...
+
+``--resident`` uploads the frames (and the labels) ONCE and keeps them in HBM: the train / val recipes are drawn on the device
+(csrc/recipe_draw.hip: dpc_draw_recipe_ex), the clips gathered from the store and the labels by ``video_idx``
+(data.ResidentLabelledSource -> engine.load_resident): no host work per step, and under ``--graph`` all of it inside the replayed
+graph.  The draws are Philox words, not those of Python's ``random``: a ``--resident`` run sees a different, equally distributed
+sample of clips than the run without it.  ``--test`` / ``--retrieval`` with it read every video as a slice of the store: the
+same launches on the same bytes, no upload per video.
 ``--pretrain`` loads a DPC-RNN checkpoint
 by key intersection (neq_load_customized, backbone/resnet_2d3d.py:310-333): backbone + ConvGRU weights are taken, the
 running buffers and the head stay at their initial values -- exactly what the reference does with its own checkpoints.
@@ -100,6 +109,15 @@ def build_parser() -> argparse.ArgumentParser:
                         'of this build -- pass that sample here)')
     parser.add_argument('--val_labels', default='', type=str, help='labels of --val_frames')
     parser.add_argument('--val_lengths', default='', type=str, help='lengths of --val_frames')
+    parser.add_argument('--resident', action='store_true', help='hold the --frames array and its labels in HBM (uploaded once; every GPU holds '
+                        'a whole copy) and draw the train / val recipes on the device: no host work per step, and under --graph the draw, '
+                        'the gather and the labels are part of the replayed graph.  The draws come from Philox, not from Python\'s random: '
+                        'the clips are a different, equally distributed sample than a run without --resident sees.  --test / --retrieval '
+                        'read each video as a slice of the store (same results, no upload per video).  Needs --frames')
+    parser.add_argument('--offsets', default='', type=str, help='int64 .npy [videos + 1]: --frames is then a packed uint8 array '
+                        '[total_frames, H0, W0, 3] of videos of any length, video v = frames[offsets[v]:offsets[v + 1]] (instead of '
+                        '--lengths).  Needs --resident')
+    parser.add_argument('--val_offsets', default='', type=str, help='offsets of --val_frames')
     parser.add_argument('--crop', default=224, type=int, help='side of RandomSizedCrop / CenterCrop in the recipes (eval/test.py:122,162,170)')
     parser.add_argument('--graph', action='store_true', help='after two eager train steps and one eager validation step, replay ONE captured '
                         'hipGraph per kind of step (HIP device only; a changed learning rate captures a new step).  Synthetic input: batch '
@@ -145,9 +163,9 @@ def retrieval(args, eng, mk, dev, log, num_epoch: int, probe=None):
     ks = retrieval_ks(args.retrieval_k)
     t0 = time.time()
 
-    def embed(frames, labels, lengths):
-        src = mk(frames, labels, lengths, 'test')
-        if not src.keep:
+    def embed(frames, labels, lengths, offsets=''):
+        src = mk(frames, labels, lengths, 'test', offsets) if args.resident else mk(frames, labels, lengths, 'test')
+        if len(src.keep) == 0:
             raise ValueError('no video of %s is long enough for %d x %d frames at stride %d' % (frames, args.num_seq, args.seq_len, args.ds))
         emb = torch.zeros(len(src.keep), eng.D, dtype=torch.float32, device=dev)
         labs = []
@@ -156,7 +174,7 @@ def retrieval(args, eng, mk, dev, log, num_epoch: int, probe=None):
             labs.append(label)
         return emb, torch.tensor(labs, dtype=torch.int64).to(dev), src.skipped
 
-    q_emb, q_lab, skipped = embed(args.frames, args.labels, args.lengths)
+    q_emb, q_lab, skipped = embed(args.frames, args.labels, args.lengths, args.offsets)
     cross = bool(args.gallery_frames)
     if cross:
         g_emb, g_lab, g_skipped = embed(args.gallery_frames, args.gallery_labels, args.gallery_lengths)
@@ -254,12 +272,17 @@ def _worker(rank: int, world: int, args, port: int):
         log('=> train only final_bn / final_fc on a frozen backbone + ConvGRU (batch statistics, running buffers updated)')
 
     # --graph, synthetic input: `refill` draws batch and labels on the device in front of the step (inside the graph once it is a replay);
-    # --frames: load_recipe and set_labels fill operand and labels eagerly before each step and the graph starts from them.
+    # --frames: load_recipe and set_labels fill operand and labels eagerly before each step and the graph starts from them;
+    # --resident: the two refills advance their source's cursor, draw the recipe, gather clips and labels on the device
+    # (engine.load_resident) -- in front of every eager step, also without --graph, and inside the graph.  They are made ONCE: the
+    # engine's capture cache keys on their identity, and set_lr asks for a new capture after every milestone.
     # lr / wd / the segment table are baked into a capture: set_lr drops the driver's handles, and the next step asks the engine again
     # -- the replay that exists when nothing changed, a new capture (the old one stays parked) when the schedule passed a milestone
     allreduce = make_allreduce(dist, world)
-    refill = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
-    steps = StepDriver(eng, args.graph, allreduce, refill, refill)
+    refill = refill_val = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
+    if args.resident:
+        refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
+    steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def set_lr(mult, saved=None):
         """the schedule scales every group; saved: the groups' lrs of a resumed checkpoint"""
@@ -320,11 +343,22 @@ def _worker(rank: int, world: int, args, port: int):
         np.random.seed(rank)      # as dpc_amd.main: one stream per rank like one per loader worker (eval/test.py seeds nothing)
         mk = lambda fr, lb, ln, recipe: LabelledFrameSource(fr, lb, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu,  # noqa: E731
                                                             args.num_class, recipe, ln or None, rank, world, args.crop)
+        if args.resident:   # every store goes to HBM once; a source is a view of one with its own recipe and draw stream
+            from .data import FrameStore, ResidentLabelledSource
+            stores = {}
+
+            def mk(fr, lb, ln, recipe, offsets='', role=0):
+                key = (fr, ln or '', offsets)
+                if key not in stores:
+                    stores[key] = FrameStore(fr, offsets or None, ln or None).to_device(dev, reserve=eng.resident_reserve())
+                # Philox keys: the rank in the low word, the role (0 train, 1 validation) in the high one -- never seed + k (csrc/philox.h)
+                return ResidentLabelledSource(stores[key], lb, args.dataset, args.num_seq, args.seq_len, args.ds, args.img_dim, per_gpu,
+                                              args.num_class, dev, recipe, rank, world, args.crop, seed=(role << 32) | rank)
         if args.retrieval:
             retrieval(args, eng, mk, dev, log, num_epoch, probe)
             return
         if args.test:
-            src_test = mk(args.frames, args.labels, args.lengths, 'test')
+            src_test = mk(args.frames, args.labels, args.lengths, 'test', args.offsets) if args.resident else mk(args.frames, args.labels, args.lengths, 'test')
             t0 = time.time()
             eng.test_reset()
             for _, frames, label, starts, clip in src_test.videos():
@@ -345,8 +379,18 @@ def _worker(rank: int, world: int, args, port: int):
                             'flat_p': eng.flat_p.detach().cpu(), 'flat_m': eng.flat_m.detach().cpu(), 'step': eng.step_count},
                            os.path.join(probe, f'rank{rank}.pt'))
             return
-        src_train = mk(args.frames, args.labels, args.lengths, 'train')
-        src_val = mk(args.val_frames, args.val_labels, args.val_lengths, 'val') if args.val_frames else mk(args.frames, args.labels, args.lengths, 'val')
+        if args.resident:
+            src_train = mk(args.frames, args.labels, args.lengths, 'train', args.offsets, 0)
+            src_val = (mk(args.val_frames, args.val_labels, args.val_lengths, 'val', args.val_offsets, 1) if args.val_frames
+                       else mk(args.frames, args.labels, args.lengths, 'val', args.offsets, 1))
+            # the draw counters are not in the checkpoint: a resumed run derives them from the epochs already run, which is what they were
+            src_train.set_draw(args.start_epoch * len(src_train))
+            src_val.set_draw(args.start_epoch * len(src_val))
+            if src_train.skipped or src_val.skipped:
+                log('{0} training / {1} validation videos skipped (too short for one clip)'.format(src_train.skipped, src_val.skipped), flush=True)
+        else:
+            src_train = mk(args.frames, args.labels, args.lengths, 'train')
+            src_val = mk(args.val_frames, args.val_labels, args.val_lengths, 'val') if args.val_frames else mk(args.frames, args.labels, args.lengths, 'val')
     gen = torch.Generator(dev).manual_seed(1000 + rank)
     shape = (per_gpu, args.num_seq, 3, args.seq_len, args.img_dim, args.img_dim)
 
@@ -378,7 +422,7 @@ def _worker(rank: int, world: int, args, port: int):
             if feed is not None:
                 frames, starts, clips, y = next(feed)
                 eng.load_recipe(frames, starts, clips, ds=args.ds)   # fills the stem's operand; no f32 video in between
-            elif not args.graph:
+            elif not args.graph and not args.resident:   # --resident: the refill has filled operand and labels
                 x, y = batch()
 
             def eager():
@@ -392,7 +436,9 @@ def _worker(rank: int, world: int, args, port: int):
 
         for epoch in range(args.start_epoch, args.epochs):
             n_train = len(src_train) if src_train is not None else args.synthetic
-            feed = src_train.epoch(dev) if src_train is not None else None
+            feed = src_train.epoch(dev) if src_train is not None and not args.resident else None
+            if args.resident:
+                src_train.begin_epoch()   # the epoch's permutation to the device, the cursor to 0: the one host-to-device copy of the epoch
             for idx in range(n_train):  # train(): eval/test.py:218-271
                 res = step(True, feed)
                 if idx % args.print_freq == 0:
@@ -405,7 +451,9 @@ def _worker(rank: int, world: int, args, port: int):
                 log(line, flush=True)
             vl = va = 0.0
             n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
-            feed = src_val.epoch(dev) if src_val is not None else None
+            feed = src_val.epoch(dev) if src_val is not None and not args.resident else None
+            if args.resident:
+                src_val.begin_epoch()
             for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
                 loss, acc = reduce(step(False, feed))
                 vl += loss
@@ -436,6 +484,14 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     world = world_size(args)
+    if args.resident and not args.frames:
+        raise ValueError('--resident holds the --frames array in HBM: --frames is missing')
+    if (args.offsets or args.val_offsets) and not args.resident:
+        raise ValueError('--offsets describes a packed frame store, which only --resident reads: --resident is missing')
+    if (args.lengths and args.offsets) or (args.val_lengths and args.val_offsets):
+        raise ValueError('--lengths goes with the dense --frames array and --offsets with a packed one: pass --lengths or --offsets, not both')
+    if args.val_offsets and not args.val_frames:
+        raise ValueError('--val_offsets describes the packed store of --val_frames: --val_frames is missing')
     if args.test and args.frames and world != 1:   # the reference's DataParallel over the windows of a video is not reproduced
         raise ValueError('--test with --frames runs on one GPU (the windows of a video are chunked on it): pass --gpu 0')
     if args.retrieval:
@@ -451,7 +507,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
         if args.graph and args.retrieval_bn == 'batch':
             raise ValueError('--graph replays the eval-mode step: it cannot be combined with --retrieval_bn batch')
     if _simulator is not None and world != 1:
-        raise ValueError('the simulator runs one rank')
+        args._simulator = 'emu'   # the rank processes (gloo instead of RCCL) load the simulator themselves
     launch(_worker, args)
 
 

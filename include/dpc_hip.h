@@ -503,12 +503,30 @@ int dpc_frames_to_input_ex(const uint8_t* frames, int32_t B, int32_t F, int32_t 
  *   jitter_p < 0: the recipe has no RandomGray / ColorJitter; a jitter range of 0 leaves that step out of the chain.  flip_code:
  *   what aug.flip holds when the flip is drawn (1 after the crop, 2 before it; 0 = the recipe never flips).  One jitter draw per
  *   frame (consistent=False), which is what both pre-training recipes use.
- *   KS >= 2 ceil(max(W0, H0) / size) + 1, B <= 1024, size <= 1024. */
+ *   KS >= 2 ceil(max(W0, H0) / size) + 1, B <= 1024, size <= 1024.
+ * dpc_draw_recipe_ex: dpc_draw_recipe (same slots, same Philox stream and counter block, same arithmetic) with the pieces the
+ *   classifier's recipes (eval/test.py:161-176) need; dpc_draw_recipe is this entry with flags = 0 and the three tables NULL.
+ *   recipe->flags (undefined bits: DPC_ERR_ARG):
+ *     DPC_RECIPE_JITTER_CONSISTENT   ColorJitter(consistent=True), utils/augmentation.py:330-333: when the jitter `p` draw (slot 5)
+ *       passes, ONE get_params draw from FRAME 0's slots 58 + {2 .. 8}, copied to every frame of the clip; when it fails every frame
+ *       gets order = 255....  Slots 2 .. 8 of frames >= 1 are unused.
+ *     DPC_RECIPE_SCALE_AFTER_SIZED   RandomSizedCrop(crop, BILINEAR, p = sized_p) followed by NEAREST Scale((size, size)); needs
+ *       sized_p >= 0.  PIL's resize is separable and per output sample, so output row i of either axis is row
+ *       t = scale_tab ? scale_tab[i] : i of the table that resizes to `crop`: an accepted attempt {in = w, out = crop}, row t; ten
+ *       rejected attempts: ow / oh computed with `crop`, first = rint((ow - crop) / 2), row first + t; the failed `p` draw,
+ *       CenterCrop(crop): x1 = rint((W0 - crop) / 2), one tap at index t.  KS >= 2 ceil(max(W0, H0) / crop) + 1; scale_tab
+ *       (int32 [size], values in [0, crop)) is required iff crop != size; crop <= 1024; sized_p < 1 with crop > W0 or crop > H0 is
+ *       DPC_ERR_UNSUPPORTED (CenterCrop would leave the frame).
+ *   lengths int64 [videos] or NULL: vlen = lengths[v] instead of offsets[v + 1] - offsets[v] -- a dense store whose videos are
+ *     shorter than their slot (the caller has dropped videos with lengths[v] <= N*SL*ds).
+ *   labels int64 [videos] with target int64 [B], both or neither: the same launch writes target[b] = labels[video of clip b]. */
 #define DPC_RECIPE_SLOTS(n_frames) (58 + 9 * (n_frames))
+#define DPC_RECIPE_JITTER_CONSISTENT 1
+#define DPC_RECIPE_SCALE_AFTER_SIZED 2
 typedef struct dpc_recipe_desc {
     double sized_p, gray_p, jitter_p;
     double brightness, contrast, saturation, hue;
-    int32_t flip_code, reserved;
+    int32_t flip_code, flags;   /* flags: DPC_RECIPE_*; dpc_draw_recipe ignores them */
 } dpc_recipe_desc;
 int dpc_store_to_input(const uint8_t* store, int32_t B, int64_t total_frames, int32_t H0, int32_t W0, const dpc_clip_aug* aug,
                        const int8_t* gray, int32_t N, int32_t SL, int32_t ds, int32_t H, int32_t W, const dpc_resample* rs,
@@ -519,6 +537,11 @@ int dpc_draw_recipe(const dpc_recipe_desc* recipe, const int32_t* video_idx, con
                     const int32_t* scale_tab, uint64_t seed, const int32_t* draw_dev, const float* uniforms, dpc_clip_aug* aug,
                     int64_t* clip_first, int8_t* gray, dpc_frame_jitter* jitter, int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk,
                     dpc_stream_t stream);
+int dpc_draw_recipe_ex(const dpc_recipe_desc* recipe, const int32_t* video_idx, const int32_t* step_dev, const int64_t* offsets,
+                       const int64_t* lengths, const int64_t* labels, int32_t B, int32_t W0, int32_t H0, int32_t crop, int32_t size,
+                       int32_t N, int32_t SL, int32_t ds, int32_t KS, const int32_t* scale_tab, uint64_t seed, const int32_t* draw_dev,
+                       const float* uniforms, dpc_clip_aug* aug, int64_t* clip_first, int8_t* gray, dpc_frame_jitter* jitter,
+                       int32_t* xb, int32_t* xk, int32_t* yb, int32_t* yk, int64_t* target, dpc_stream_t stream);
 
 /* The test-time windows of eval/dataset_3d_lc.py:109-127 from ONE resident video: `video` u8 [F][H0][W0][3] is read by every clip
  * of the batch, clip b = the window whose first frame is aug[b].start (aug[b].flip as above; the test transform never flips).
