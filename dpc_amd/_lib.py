@@ -65,6 +65,15 @@ class AdamSegment(C.Structure):
 ADAM_MAX_SEGMENTS = 512   # DPC_ADAM_MAX_SEGMENTS
 
 
+class GradState(C.Structure):
+    """struct dpc_grad_state (include/dpc_hip.h): the gradient guard's verdict, in device memory"""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int32), ("n_skipped", C.c_int32),
+                ("n_clipped", C.c_int32), ("reserved", C.c_int32)]
+
+
+GRAD_PARTIALS = 1024   # DPC_GRAD_PARTIALS
+
+
 class ConvEpilogue(C.Structure):
     """struct dpc_conv_epilogue (include/dpc_hip.h)"""
     _fields_ = [(n, C.c_void_p) for n in ("addend", "addend_mask", "bn_raw", "bn_mask", "bn_mean", "bn_invstd", "stats")]
@@ -148,6 +157,12 @@ _SIGS = {
     "dpc_step_advance": [_vp, _vp, _f64, _f64, _vp],
     "dpc_adam_dev": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp],
     "dpc_adam_groups_dev": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp],
+    "dpc_grad_sumsq": [_vp, _i64, _vp, _i32, _vp, _vp],
+    "dpc_grad_verdict": [_vp, _i32, _f64, _i32, _vp, _vp],
+    "dpc_step_advance_gated": [_vp, _vp, _f64, _f64, _vp, _vp],
+    "dpc_adam_dev_ex": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp],
+    "dpc_adam_groups_dev_ex": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp],
+    "dpc_grad_scale": [_vp, _i64, _vp, _i32, _vp, _vp],
     "dpc_counter_advance": [_vp, _vp],
     "dpc_copy2d_f32": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "dpc_copy2d_multi": [_vp, _i32, _i32, _vp],

@@ -392,7 +392,12 @@ extern "C" int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream_) {
 }
 
 __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long long n4, long long n, float lr, float b1,
-                                float b2, float omb1, float omb2, float eps, float wd, const float* bc, float gscale) {
+                                float b2, float omb1, float omb2, float eps, float wd, const float* bc, float gscale,
+                                const dpc_grad_state* gs) {
+    if (gs) {   // the gradient guard's verdict (grad_guard.hip): a skipped step loads and stores nothing
+        if (gs->skip) return;
+        gscale = gscale * gs->coef;
+    }
     const float step = lr / bc[0];
     const float isb2 = 1.f / sqrtf(bc[1]);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -419,13 +424,20 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, lo
 }
 
 // betas arrive as doubles: 1 - beta2 is formed in double like torch does (1 - 0.999f would be off by 1.3e-5 relative)
-extern "C" int dpc_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
-                            float eps, float wd, const float* bias_corr_dev, float grad_scale, dpc_stream_t stream_) {
+// state_dev: the gradient guard's verdict, or null (dpc_adam_dev)
+extern "C" int dpc_adam_dev_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
+                               float eps, float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev,
+                               dpc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!p || !g || !m || !v || n <= 0 || !bias_corr_dev) return DPC_ERR_ARG;
     const long long n4 = (n + 3) / 4;
-    DPC_LAUNCH(adam_dev_kernel, dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale);
+    DPC_LAUNCH(adam_dev_kernel, dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev);
     return dpc_launch_status();
+}
+
+extern "C" int dpc_adam_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
+                            float eps, float wd, const float* bias_corr_dev, float grad_scale, dpc_stream_t stream_) {
+    return dpc_adam_dev_ex(p, g, m, v, n, lr, beta1, beta2, eps, wd, bias_corr_dev, grad_scale, nullptr, stream_);
 }
 
 extern "C" int dpc_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -447,7 +459,12 @@ extern "C" int dpc_adam(float* p, const float* g, float* m, float* v, int64_t n,
 constexpr int ADAM_TILE4 = 1024;  // 16-byte units per tile: 4 per thread, 16 KB of each arena
 __global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float* g, float* m, float* v, long long n4, long long ntiles,
                                                           const dpc_adam_segment* segs, int nseg, float b1, float b2, float omb1,
-                                                          float omb2, float eps, const float* bc, float gscale) {
+                                                          float omb2, float eps, const float* bc, float gscale,
+                                                          const dpc_grad_state* gs) {
+    if (gs) {   // as in adam_dev_kernel
+        if (gs->skip) return;
+        gscale = gscale * gs->coef;
+    }
     __shared__ long long s_begin[DPC_ADAM_MAX_SEGMENTS], s_end[DPC_ADAM_MAX_SEGMENTS];
     __shared__ float s_lr[DPC_ADAM_MAX_SEGMENTS], s_wd[DPC_ADAM_MAX_SEGMENTS];   // lr < 0 marks an inactive segment
     const int tid = threadIdx.x;
@@ -492,15 +509,21 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float*
 
 // n: floats in each arena, a multiple of 4 (the arenas keep every tensor 16-byte aligned).  The table is validated where it is built
 // (dpc_amd/engine.py: sorted, aligned, inside the arena); here only pointers and counts are.
-extern "C" int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
-                                   int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
-                                   float grad_scale, dpc_stream_t stream_) {
+extern "C" int dpc_adam_groups_dev_ex(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                                      int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
+                                      float grad_scale, const dpc_grad_state* state_dev, dpc_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!p || !g || !m || !v || n <= 0 || n % 4 || !segments_dev || n_segments <= 0 || n_segments > DPC_ADAM_MAX_SEGMENTS || !bias_corr_dev)
         return DPC_ERR_ARG;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16) return DPC_ERR_ARG;
     const long long n4 = n / 4, ntiles = (n4 + ADAM_TILE4 - 1) / ADAM_TILE4;
     const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
-    DPC_LAUNCH(adam_groups_kernel, dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale);
+    DPC_LAUNCH(adam_groups_kernel, dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev);
     return dpc_launch_status();
+}
+
+extern "C" int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                                   int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
+                                   float grad_scale, dpc_stream_t stream_) {
+    return dpc_adam_groups_dev_ex(p, g, m, v, n, segments_dev, n_segments, beta1, beta2, eps, bias_corr_dev, grad_scale, nullptr, stream_);
 }

@@ -537,6 +537,8 @@ class BackboneEngine:
         self._scratch: Dict[Tuple[int, ...], List[torch.Tensor]] = {}
         self._step_count = 0
         self._groups, self._groups_key, self._seg_host, self._seg_dev, self._seg_n = None, None, None, None, 0   # parameter groups of the fused Adam (set_param_groups)
+        self._guard, self._guard_state, self._guard_partials = None, None, None   # gradient guard of the fused Adam (set_grad_guard)
+        self._steps_unsure = False   # a step may have been skipped on the device since _step_count was last read from dev_step
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -901,10 +903,14 @@ class BackboneEngine:
         self.dev_step.copy_(old.dev_step)
         self.dev_bc.copy_(old.dev_bc)
         self.dev_draw.copy_(old.dev_draw)
-        self._step_count = old._step_count
+        self._step_count, self._steps_unsure = old._step_count, old._steps_unsure
         self.lr, self.wd = old.lr, old.wd
         if old.param_groups:
             self.set_param_groups(old.param_groups)
+        if old._guard_state is not None:   # the guard's settings and its counters
+            self._guard_alloc()
+            self._guard_state.copy_(old._guard_state)
+            self._guard = old._guard
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1060,12 +1066,20 @@ class BackboneEngine:
 
     @property
     def step_count(self) -> int:
-        """completed optimizer steps (host mirror of dev_step)"""
+        """completed optimizer steps (host mirror of dev_step).  The gradient guard drops a non-finite step on the device, so while
+        it may have done so the mirror is refreshed from dev_step here -- one read-back where somebody asks (a checkpoint, a probe),
+        none in the step."""
+        if self._steps_unsure:
+            t = int(self.dev_step.item())
+            if t != self._step_count:
+                self._step_count = t
+                self.packed_for_step = -1   # (the re-pack cache is keyed on the mirror: do not let the new value match an old key)
+            self._steps_unsure = False
         return self._step_count
 
     @step_count.setter
     def step_count(self, t: int):  # checkpoint resume: host value -> device counter
-        self._step_count = int(t)
+        self._step_count, self._steps_unsure = int(t), False
         self.dev_step.fill_(int(t))
         self.dev_draw.fill_(int(t))  # one draw per step in the engine-owned loop: a resumed run continues the same mask stream
 
@@ -1152,8 +1166,70 @@ class BackboneEngine:
         live = {k for g in self._groups if not g["frozen"] for k in g["params"]}
         return [k for k in self.offsets if k not in live]
 
-    def adam_step(self, grad_scale: float = 1.0):
+    def set_grad_guard(self, max_norm: Optional[float] = None, skip_nonfinite: bool = False):
+        """Gradient guard of the fused Adam (csrc/grad_guard.hip), decided on the device between the gradient exchange and the update:
+        max_norm: clip the gradient's global 2-norm over the live parameters (those the grouped update would touch) to it, by torch's
+        clip_grad_norm_ formula, the factor folded into the update -- flat_g itself is not rewritten; skip_nonfinite: an Inf or NaN
+        anywhere in the live gradient suppresses the whole step -- flat_p / flat_m / flat_v, dev_step and the bias corrections keep
+        their bits, and the step does not count as an optimizer step.  The defaults turn the guard off: adam_step() then launches
+        exactly what it launched without it.
+
+        The partial sums and the 32-byte verdict record (zeroed) are allocated at the first enabling -- do that before a step is
+        captured, a captured step allocates nothing.  The settings are among the scalars a captured step bakes in: a replay after they
+        changed raises.  grad_stats() reads the record."""
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not (math.isfinite(max_norm) and max_norm > 0.0):
+                raise ValueError(f"set_grad_guard: max_norm must be None or a finite positive number, got {max_norm}")
+        guard = (max_norm, bool(skip_nonfinite)) if (max_norm is not None or skip_nonfinite) else None
+        if guard is not None:
+            self._guard_alloc()
+        self._guard = guard
+
+    def _guard_alloc(self):
+        if self._guard_state is None:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise L.DpcError("set_grad_guard: enable the guard before a step is captured (it allocates its device record)")
+            self._guard_partials = torch.zeros(L.GRAD_PARTIALS, dtype=torch.float64, device=self.device)
+            self._guard_state = torch.zeros(C.sizeof(L.GradState), dtype=torch.uint8, device=self.device)
+
+    @property
+    def grad_guard(self):
+        """(max_norm or None, skip_nonfinite), or None while the guard is off"""
+        return self._guard
+
+    def grad_stats(self) -> dict:
+        """the guard's verdict on the last guarded step and its running counts: norm, coef, skip, n_skipped, n_clipped, sumsq.
+        One 32-byte device-to-host copy; the step itself never calls it."""
+        if self._guard_state is None:
+            raise RuntimeError("grad_stats: the gradient guard was never enabled (set_grad_guard)")
+        st = L.GradState.from_buffer_copy(self._guard_state.cpu().numpy().tobytes())
+        return {"norm": st.norm, "coef": st.coef, "skip": st.skip, "n_skipped": st.n_skipped, "n_clipped": st.n_clipped, "sumsq": st.sumsq}
+
+    def _count_step(self):
+        """one more attempted optimizer step on the host mirror; with skip_nonfinite the device may have counted none"""
         self._step_count += 1
+        if self._guard is not None and self._guard[1]:
+            self._steps_unsure = True
+
+    def adam_step(self, grad_scale: float = 1.0):
+        self._count_step()
+        if self._guard is not None:
+            # Runs after the gradient exchange: every rank reduces the same all-reduced arena with the same work split and the same
+            # summation order, so all ranks reach the same verdict bit for bit -- no collective, no host.
+            max_norm, skip_nonfinite = self._guard
+            seg, nseg = (self._seg_dev, self._seg_n) if self._groups else (None, 0)
+            st = self._guard_state
+            self.call("dpc_grad_sumsq", self.flat_g, self.numel, seg, nseg, self._guard_partials)
+            self.call("dpc_grad_verdict", self._guard_partials, L.GRAD_PARTIALS, max_norm or 0.0, int(skip_nonfinite), st)
+            self.call("dpc_step_advance_gated", self.dev_step, self.dev_bc, 0.9, 0.999, st)
+            if self._groups:
+                self.call("dpc_adam_groups_dev_ex", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, seg, nseg,
+                          0.9, 0.999, 1e-8, self.dev_bc, grad_scale, st)
+            else:
+                self.call("dpc_adam_dev_ex", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
+                          self.wd, self.dev_bc, grad_scale, st)
+            return
         self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
         if self._groups:
             self.call("dpc_adam_groups_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self._seg_dev, self._seg_n,
@@ -1183,7 +1259,10 @@ class BackboneEngine:
         gd = self.gru_desc
         base = (float(self.lr), float(self.wd), float(gd.p_drop), int(gd.seed))
         # with parameter groups the captured update reads the segment table: its contents belong to what a replay must still find
-        return base + ((self._seg_n, self._seg_host),) if self._groups else base
+        if self._groups:
+            base = base + ((self._seg_n, self._seg_host),)
+        # ... and with the gradient guard its two settings (only then: the keys of unguarded runs stay what they were)
+        return base + (("grad_guard",) + self._guard,) if self._guard is not None else base
 
     def check_graph_capture(self):
         """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
@@ -1253,7 +1332,7 @@ class BackboneEngine:
             if eng is None:
                 raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
             if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
-                raise RuntimeError(f"lr / wd / dropout changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
+                raise RuntimeError(f"lr / wd / dropout / gradient guard changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
                                    f"call {again}")
             return run(eng, graphs)
 
@@ -1323,9 +1402,9 @@ class BackboneEngine:
                 self.backward(on_tail_ready=cut if two_bucket else None)
                 if allreduce is not None:
                     cut()
-            host_steps = self._step_count
+            host_steps, unsure = self._step_count, self._steps_unsure
             self.adam_step()
-            self._step_count = host_steps  # capture executes nothing
+            self._step_count, self._steps_unsure = host_steps, unsure  # capture executes nothing
 
         def run(eng, graphs):
             graphs[0].replay()
@@ -1338,7 +1417,7 @@ class BackboneEngine:
             elif allreduce is not None:
                 allreduce(whole)
                 graphs[1].replay()
-            eng._step_count += 1
+            eng._count_step()
             eng.packed_for_step = -1
             return result
 

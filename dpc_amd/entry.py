@@ -61,6 +61,43 @@ def average_over_ranks(dist, vals: torch.Tensor, world: int) -> torch.Tensor:
     return vals
 
 
+def add_guard_flags(parser):
+    """--clip_grad / --skip_nonfinite of both entries (BackboneEngine.set_grad_guard)"""
+    parser.add_argument('--clip_grad', default=0.0, type=float, help='clip the global 2-norm of the gradient to this value inside the fused '
+                        'step, on the device (torch.nn.utils.clip_grad_norm_\'s formula; works under --graph and --resident).  0 = off')
+    parser.add_argument('--skip_nonfinite', action='store_true', help='drop an optimizer step whose gradient holds an Inf or NaN: parameters, '
+                        'Adam moments and the step count keep their values, decided on the device.  With this or --clip_grad every printed '
+                        'train line ends in the gradient norm and every training epoch in a "Grad guard:" line')
+
+
+class GuardLog:
+    """What the entries print about the gradient guard.  ``open`` turns the guard on from the flags (before any step is captured) and
+    returns None without them -- the output then stays byte for byte what it was."""
+
+    def __init__(self, eng):
+        self.eng, self.seen = eng, (0, 0)
+
+    @classmethod
+    def open(cls, eng, args):
+        if not args.clip_grad >= 0.0:
+            raise ValueError('--clip_grad must not be negative')
+        if not (args.clip_grad > 0.0 or args.skip_nonfinite):
+            return None
+        eng.set_grad_guard(args.clip_grad if args.clip_grad > 0.0 else None, args.skip_nonfinite)
+        return cls(eng)
+
+    def gnorm(self) -> str:
+        """tail of a printed train line: the norm of the step just taken (one 32-byte copy; every rank holds the same value)"""
+        return ' gnorm {:.4f}'.format(self.eng.grad_stats()['norm'])
+
+    def epoch_line(self, steps: int) -> str:
+        st = self.eng.grad_stats()
+        now = (st['n_skipped'], st['n_clipped'])
+        skipped, clipped = now[0] - self.seen[0], now[1] - self.seen[1]
+        self.seen = now
+        return 'Grad guard: {0} skipped, {1} clipped of {2} steps'.format(skipped, clipped, steps)
+
+
 class StepDriver:
     """The steps of a run, eager or replayed.  Without ``graph`` every step is eager.  With it, per RUN (not per epoch) the first two
     train steps and the first validation step are eager -- they size every lazy buffer --; from then on the engine is asked once

@@ -66,7 +66,7 @@ import time
 
 import torch
 
-from .entry import StepDriver, average_over_ranks, launch, open_rank, world_size
+from .entry import GuardLog, StepDriver, average_over_ranks, add_guard_flags, launch, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -135,6 +135,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--retrieval_bn', default='running', choices=['running', 'batch'], help='BatchNorm3d of the embedding forward: '
                         'running = eval mode, right for any checkpoint of this entry; batch = the statistics of each chunk of '
                         'windows, for a DPC checkpoint, which carries no running statistics (an embedding then depends on its chunk)')
+    add_guard_flags(parser)
     return parser
 
 
@@ -282,6 +283,9 @@ def _worker(rank: int, world: int, args, port: int):
     refill = refill_val = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
     if args.resident:
         refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
+    # the gradient guard is on before the first capture and stays on: its settings are among the baked values, so the captures
+    # set_lr asks for after a milestone carry it too
+    guard = GuardLog.open(eng, args)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def set_lr(mult, saved=None):
@@ -443,12 +447,14 @@ def _worker(rank: int, world: int, args, port: int):
                 res = step(True, feed)
                 if idx % args.print_freq == 0:
                     loss, acc = reduce(res)
-                    log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr),
-                        flush=True)
+                    log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr) +
+                        (guard.gnorm() if guard and rank == 0 else ''), flush=True)
                     iteration += 1  # advanced on logged steps only, as the reference does (eval/test.py:262-270)
             line = steps.replay_line(args.batch_size)
             if line:
                 log(line, flush=True)
+            if guard and rank == 0:
+                log(guard.epoch_line(n_train), flush=True)
             vl = va = 0.0
             n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
             feed = src_val.epoch(dev) if src_val is not None and not args.resident else None

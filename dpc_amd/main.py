@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from .entry import StepDriver, average_over_ranks, launch, open_rank, world_size
+from .entry import GuardLog, StepDriver, average_over_ranks, add_guard_flags, launch, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -75,6 +75,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--offsets', default='', type=str, help='int64 .npy [videos + 1]: --frames is then a packed uint8 array '
                         '[total_frames, H0, W0, 3] of videos of any length, video v = frames[offsets[v]:offsets[v + 1]].  Needs --resident')
     parser.add_argument('--val_offsets', default='', type=str, help='--offsets of the --val_frames array')
+    add_guard_flags(parser)
     return parser
 
 
@@ -187,6 +188,7 @@ def _worker(rank: int, world: int, args, port: int):
     refill = refill_val = (lambda: eng.fill_synthetic(1000 + rank)) if args.graph and not args.frames else None
     if args.resident:
         refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
+    guard = GuardLog.open(eng, args)   # before the first capture: the guard's settings are baked into a captured step
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def validate(block):   # validate(): dropout off, BN still batch statistics (dpc/main.py:249-282, model_3d.py:28)
@@ -218,12 +220,14 @@ def _worker(rank: int, world: int, args, port: int):
                     a.update(v, per_gpu)
                 if train and rank == 0:
                     print('Epoch: [{0}][{1}/{2}]\t Loss {3:.6f} ({4:.4f})\t Acc: top1 {5:.4f}; top3 {6:.4f}; top5 {7:.4f} T:{8:.2f}\t'.format(
-                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic), flush=True)
+                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else ''), flush=True)
                 if train:
                     iteration += 1
         line = steps.replay_line(args.batch_size)
         if line and rank == 0:
             print(line, flush=True)
+        if train and guard and rank == 0:
+            print(guard.epoch_line(n_batches), flush=True)
         return losses.local_avg, accs[0].local_avg, [a.local_avg for a in accs]
 
     for epoch in range(args.start_epoch, args.epochs):

@@ -24,17 +24,26 @@ optimizer used to read the file's first group whatever followed it).
 ``state_dict()`` / ``load_state_dict()`` speak torch.optim.Adam's layout (dpc_amd/checkpoint.py) -- with groups: one ``param_groups``
 entry per group and state only for parameters that have been updated -- so checkpoints move both ways.
 The engine is created by the module's first forward; a step before that has nothing to update and raises.
+
+Gradient guard: ``Adam(..., max_grad_norm=1.0, skip_nonfinite=True)`` clips the global 2-norm of the gradients this step updates
+and drops a step whose gradient holds an Inf or NaN, inside the fused step on the device (``BackboneEngine.set_grad_guard``; the
+``.grad`` tensors are not rewritten).  ``clip_grad_norm_(parameters, max_norm)`` is ``torch.nn.utils.clip_grad_norm_`` over the
+arena: three launches whatever the number of parameters, the norm returned as a device tensor.
 """
 from __future__ import annotations
 
 import torch
 
+import ctypes as C
+
+from . import _lib as L
 from . import checkpoint as ckpt
 from .engine import engine_of
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False,
+                 max_grad_norm=None, skip_nonfinite: bool = False):
         if amsgrad:
             raise ValueError("amsgrad is not supported (the reference does not use it, dpc/main.py:80-81)")
         if tuple(betas) != (0.9, 0.999) or eps != 1e-8:
@@ -47,6 +56,9 @@ class Adam(torch.optim.Optimizer):
         for g in self.param_groups:
             if g.get("amsgrad") or tuple(g["betas"]) != (0.9, 0.999) or g["eps"] != 1e-8:
                 raise ValueError("dpc_amd.optim.Adam runs the reference's configuration in every group: betas (0.9, 0.999), eps 1e-8, no amsgrad")
+        if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < float("inf")):
+            raise ValueError(f"max_grad_norm must be None or a finite positive number, got {max_grad_norm}")
+        self._guard = (max_grad_norm, bool(skip_nonfinite))   # (None, False): the engine's guard is left as it is
         self._pending_state = None
         self._by_ptr = None     # (engine, {arena address: parameter name})
         self._updated = set()   # names of the parameters that have been updated at least once (torch creates their state then)
@@ -101,6 +113,8 @@ class Adam(torch.optim.Optimizer):
                 return loss   # nothing has a gradient: torch's step would do nothing either
             eng.set_param_groups([{"params": have, "lr": float(g["lr"]), "weight_decay": float(g["weight_decay"])}
                                   for g, have in zip(self.param_groups, live)])
+        if self._guard != (None, False):
+            eng.set_grad_guard(*self._guard)
         eng.adam_step()
         self._updated.update(k for have in live for k in have)
         eng.packed_for_step = -1
@@ -140,3 +154,59 @@ class Adam(torch.optim.Optimizer):
             self._pending_state = state_dict   # the engine does not exist yet: applied at the first step
             return
         self._load_into(eng, names, state_dict)
+
+
+def _arena_names(params, who: str):
+    """(engine, names) of parameters that are views of ONE engine's arena"""
+    eng = engine_of(params[0]) if params else None
+    if eng is None:
+        raise RuntimeError(f"{who}: the parameters are not backed by an engine yet -- run a forward of the "
+                           "dpc_amd module (DPC_RNN / LC) they belong to first (it moves them into the engine's arena)")
+    by_ptr = {t.data_ptr(): k for k, t in eng.PRM.items()}
+    names = [by_ptr.get(p.data_ptr()) for p in params]
+    if any(k is None for k in names):
+        raise RuntimeError(f"{who} works on parameters of ONE dpc_amd module (views of its engine's arena)")
+    return eng, names
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (2-norm) over the engine's gradient arena: the total norm of the
+    gradients of the given parameters that have one, then those gradients scaled in place by ``min(1, max_norm / (norm + 1e-6))``.
+    Returns the norm as a 0-dim f32 device tensor (no read-back).  A non-finite norm is returned as such and nothing is scaled; it
+    never skips anything.  dpc_grad_sumsq -> dpc_grad_verdict -> dpc_grad_scale over a segment table of the parameters' slices."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = list(parameters)
+    max_norm = float(max_norm)
+    eng, names = _arena_names(params, "dpc_amd.optim.clip_grad_norm_")
+    have = []
+    for p, k in zip(params, names):
+        if p.grad is None:
+            continue
+        if p.grad.data_ptr() != eng.G[k].data_ptr():   # a gradient that did not come from the engine's backward: bring it in, as step() does
+            eng.G[k].copy_(p.grad)
+        have.append((p, k))
+    if not have:
+        return torch.zeros((), dtype=torch.float32, device=eng.device)
+    live = {k for _, k in have}
+    segs = []   # the parameters' 16-byte slots in arena order, neighbours merged (engine.set_param_groups builds its table the same way)
+    for k, (o, n) in eng.offsets.items():
+        if k not in live:
+            continue
+        e = o + (n + 3) // 4 * 4
+        if segs and segs[-1][1] == o:
+            segs[-1][1] = e
+        else:
+            segs.append([o, e])
+    tab = (L.AdamSegment * len(segs))(*[L.AdamSegment(b, e, 0.0, 0.0, 1, 0) for b, e in segs])
+    tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(eng.device)
+    partials = torch.empty(L.GRAD_PARTIALS, dtype=torch.float64, device=eng.device)
+    state = torch.zeros(C.sizeof(L.GradState), dtype=torch.uint8, device=eng.device)
+    eng.call("dpc_grad_sumsq", eng.flat_g, eng.numel, tab_dev, len(segs), partials)
+    eng.call("dpc_grad_verdict", partials, L.GRAD_PARTIALS, max_norm if max_norm > 0.0 else 0.0, 0, state)
+    eng.call("dpc_grad_scale", eng.flat_g, eng.numel, tab_dev, len(segs), state)
+    for p, k in have:   # a .grad that is a tensor of its own sees the scaled values too
+        if p.grad.data_ptr() != eng.G[k].data_ptr():
+            p.grad.copy_(eng.G[k])
+    return state[8:12].view(torch.float32).reshape(()).clone()

@@ -333,6 +333,45 @@ typedef struct dpc_adam_segment {
 int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
                         int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
                         dpc_stream_t stream);
+/* ---- gradient guard (csrc/grad_guard.hip): global-norm clip and non-finite skip of the fused step, decided on the device so that a
+ * replayed hipGraph step needs no host code between backward and update.  The verdict lives in a 32-byte device record:
+ *   grad_sumsq   partials[0..DPC_GRAD_PARTIALS) = f64 sums of g^2 (every element widened before it is squared) over [0, n), or, with
+ *                a dpc_adam_segment table, over its active segments only (gaps and inactive segments are never loaded).  Every slot
+ *                is written by every call.  No atomics; the work split depends on n alone and every combine has a fixed order, so the
+ *                same arena gives the same bits on every run and every rank.  n % 4 == 0, g 16-byte aligned; with a table,
+ *                1 <= n_segments <= DPC_ADAM_MAX_SEGMENTS.
+ *   grad_verdict one workgroup adds the partials in index order and writes sumsq, norm = (float)sqrt(sumsq) and, judged on the f64 sum,
+ *                  finite, max_norm > 0 : coef = min(1, max_norm / (norm + 1e-6)) (torch's clip_grad_norm_; f64, rounded once),
+ *                                         n_clipped += coef < 1
+ *                  finite, max_norm <= 0: coef = 1
+ *                  non-finite           : skip_nonfinite ? (skip = 1, coef = 0, n_skipped += 1) : (skip = 0, coef = 1)
+ *   step_advance_gated  dpc_step_advance unless state->skip
+ *   adam_dev_ex / adam_groups_dev_ex  dpc_adam_dev / dpc_adam_groups_dev with an optional state: the gradient scale becomes
+ *                grad_scale * state->coef (one f32 product); with state->skip the launch touches none of p, m, v.  A null state, or
+ *                coef == 1 and skip == 0, gives the bits of the plain entries.
+ *   grad_scale   g *= state->coef in place over the live floats; nothing when state->skip (dpc_amd.optim.clip_grad_norm_). */
+#define DPC_GRAD_PARTIALS 1024
+typedef struct dpc_grad_state {
+    double sumsq;                 /* sum of g^2 over the live floats, f64 */
+    float norm;                   /* (float)sqrt(sumsq) */
+    float coef;                   /* factor applied to the gradient this step */
+    int32_t skip;                 /* 1: this step's update is suppressed */
+    int32_t n_skipped, n_clipped; /* running counts since the state was zeroed */
+    int32_t reserved;
+} dpc_grad_state;
+int dpc_grad_sumsq(const float* g, int64_t n, const dpc_adam_segment* segments_dev, int32_t n_segments, double* partials,
+                   dpc_stream_t stream);
+int dpc_grad_verdict(const double* partials, int32_t n_partials, double max_norm, int32_t skip_nonfinite, dpc_grad_state* state_dev,
+                     dpc_stream_t stream);
+int dpc_step_advance_gated(int32_t* step_dev, float* bias_corr_dev, double beta1, double beta2, const dpc_grad_state* state_dev,
+                           dpc_stream_t stream);
+int dpc_adam_dev_ex(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+                    float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev, dpc_stream_t stream);
+int dpc_adam_groups_dev_ex(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                           int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
+                           const dpc_grad_state* state_dev, dpc_stream_t stream);
+int dpc_grad_scale(float* g, int64_t n, const dpc_adam_segment* segments_dev, int32_t n_segments, const dpc_grad_state* state_dev,
+                   dpc_stream_t stream);
 /* counter_dev[0] += 1 on the stream: the dropout draw counter (one draw per train-mode forward; the `step_dev` the recurrence and
  * the classifier head key their Philox masks on), graph-capturable like dpc_step_advance */
 int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream);
