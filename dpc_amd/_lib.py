@@ -163,6 +163,9 @@ _SIGS = {
     "dpc_adam_dev_ex": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp],
     "dpc_adam_groups_dev_ex": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp],
     "dpc_grad_scale": [_vp, _i64, _vp, _i32, _vp, _vp],
+    "dpc_adam_dev_ema": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
+    "dpc_adam_groups_dev_ema": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
+    "dpc_arena_swap": [_vp, _vp, _i64, _vp],
     "dpc_counter_advance": [_vp, _vp],
     "dpc_copy2d_f32": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "dpc_copy2d_multi": [_vp, _i32, _i32, _vp],

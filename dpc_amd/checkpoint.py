@@ -165,10 +165,46 @@ def load_model_state(eng, state_dict: "Dict[str, torch.Tensor]", strict: bool = 
     return missing, unexpected
 
 
+def ema_entry(eng, keys: Iterable[str]) -> dict:
+    """the checkpoint's top-level 'ema' entry while the engine keeps a parameter average (BackboneEngine.set_ema): the decay and the
+    averaged model under the keys of the file's 'state_dict', in their order (prefixed, alias keys, CPU; running buffers, which are
+    not averaged, as they are).  The reference reads named keys only, so a file with this entry still resumes there."""
+    av = eng.ema_state_dict()
+    return {"decay": float(eng.ema_decay), "state_dict": {k: av[_strip(k)].cpu() for k in keys}}
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
-    """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1)"""
-    return {"epoch": epoch, "net": net, "state_dict": model_state_dict(eng), "best_acc": best_acc,
-            "optimizer": optimizer_state_dict(eng), "iteration": iteration}
+    """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the parameter
+    average on, plus 'ema' (ema_entry)"""
+    eng._not_swapped("build_state")
+    state = {"epoch": epoch, "net": net, "state_dict": model_state_dict(eng), "best_acc": best_acc,
+             "optimizer": optimizer_state_dict(eng), "iteration": iteration}
+    if eng.ema_decay is not None:
+        state["ema"] = ema_entry(eng, state["state_dict"])
+    return state
+
+
+def averaged_state_dict(eng, ck: dict, path: str) -> "Dict[str, torch.Tensor]":
+    """the file's model with its parameters taken from ck['ema']['state_dict'] (--use_ema); buffers still come from 'state_dict'"""
+    if "ema" not in ck or "state_dict" not in ck["ema"]:
+        raise KeyError(f"{path} holds no averaged weights (no 'ema' entry: it was written without --ema)")
+    bufs = getattr(eng, "BUF", {})
+    sd = dict(ck["state_dict"])
+    sd.update({k: v for k, v in ck["ema"]["state_dict"].items() if _strip(k) not in bufs})
+    return sd
+
+
+def load_ema_state(eng, ck: dict, path: str) -> None:
+    """after the file's parameters were loaded (load_params has seeded flat_ema with them): the file's average into flat_ema.  With
+    the average off the file's entry is ignored; on and the file has none: one warning, the seed stays."""
+    if eng.ema_decay is None:
+        return
+    if "ema" not in ck:
+        warnings.warn(f"{path} holds no averaged weights: the average starts from the loaded parameters")
+        return
+    sd = {_strip(k): v for k, v in ck["ema"]["state_dict"].items()}
+    for k, (o, n) in eng.offsets.items():
+        eng.flat_ema[o:o + n].copy_(sd[k].to(torch.float32).reshape(-1))
 
 
 def save_checkpoint(state: dict, is_best: bool = False, gap: int = 1, filename: str = "models/checkpoint.pth.tar",
@@ -204,13 +240,15 @@ def resume(eng, path: str, reset_lr: bool = False) -> dict:
             eng.step_count = int(st["step"])
         else:
             warnings.warn(f"{path} holds no optimizer state: Adam moments and step count start from zero")
+    load_ema_state(eng, ck, path)
     return {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}
 
 
-def pretrain(eng, path: str, log=print) -> dict:
-    """--pretrain (dpc/main.py:104-112): key-intersection load, with the reference's report of unused keys"""
+def pretrain(eng, path: str, log=print, use_ema: bool = False) -> dict:
+    """--pretrain (dpc/main.py:104-112): key-intersection load, with the reference's report of unused keys.
+    use_ema: the parameters come from the file's averaged weights (KeyError when it has none)"""
     ck = torch.load(path, map_location="cpu", weights_only=False)
-    missing, unexpected = load_model_state(eng, ck["state_dict"], strict=False)
+    missing, unexpected = load_model_state(eng, averaged_state_dict(eng, ck, path) if use_ema else ck["state_dict"], strict=False)
     log("\n=======Check Weights Loading======")
     log("Weights not used from pretrained file:")
     for k in unexpected:

@@ -391,15 +391,29 @@ extern "C" int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream_) {
     return dpc_launch_status();
 }
 
+// ---- EMA arm of the two device-side Adam kernels (dpc_adam_dev_ema / dpc_adam_groups_dev_ema): the exponential moving average of
+// the parameters, updated by the thread that has just updated the 16-byte unit -- p_new is still in registers, so the average costs
+// one more f32 arena read and written by the kernel that already streams four; no launch of its own.
+//   e += (1 - d) (p_new - e),  d = min(decay, (1 + t) / (10 + t)),  t = step_dev[0] (the step count after this step's advance)
+// all in f32.  The lerp form has e == p as a fixed point, bit for bit.  EMA = false is the kernel as it was: same arithmetic, same order.
+__device__ __forceinline__ float ema_weight(const int32_t* step_dev, float decay) {
+    const int t = step_dev[0];
+    const float d = fminf(decay, (float)(1 + t) / (float)(10 + t));
+    return 1.f - d;
+}
+
+template <bool EMA>
 __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, long long n4, long long n, float lr, float b1,
                                 float b2, float omb1, float omb2, float eps, float wd, const float* bc, float gscale,
-                                const dpc_grad_state* gs) {
+                                const dpc_grad_state* gs, float* ema, const int32_t* step_dev, float decay) {
     if (gs) {   // the gradient guard's verdict (grad_guard.hip): a skipped step loads and stores nothing
         if (gs->skip) return;
         gscale = gscale * gs->coef;
     }
     const float step = lr / bc[0];
     const float isb2 = 1.f / sqrtf(bc[1]);
+    float omd = 0.f;
+    if constexpr (EMA) omd = ema_weight(step_dev, decay);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
         const long long base = i * 4;
         if (base + 4 <= n) {
@@ -412,12 +426,19 @@ __global__ void adam_dev_kernel(float* p, const float* g, float* m, float* v, lo
                 pv[e] -= step * mv[e] / (sqrtf(vv[e]) * isb2 + eps);
             }
             ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+            if constexpr (EMA) {
+                f32x4 ev = ((f32x4*)ema)[i];
+                DPC_UNROLL
+                for (int e = 0; e < 4; ++e) ev[e] += omd * (pv[e] - ev[e]);
+                ((f32x4*)ema)[i] = ev;
+            }
         } else {
             for (long long k = base; k < n; ++k) {
                 const float gg = g[k] * gscale + wd * p[k];
                 m[k] = b1 * m[k] + omb1 * gg;
                 v[k] = b2 * v[k] + omb2 * gg * gg;
                 p[k] -= step * m[k] / (sqrtf(v[k]) * isb2 + eps);
+                if constexpr (EMA) ema[k] += omd * (p[k] - ema[k]);
             }
         }
     }
@@ -431,7 +452,21 @@ extern "C" int dpc_adam_dev_ex(float* p, const float* g, float* m, float* v, int
     hipStream_t stream = (hipStream_t)stream_;
     if (!p || !g || !m || !v || n <= 0 || !bias_corr_dev) return DPC_ERR_ARG;
     const long long n4 = (n + 3) / 4;
-    DPC_LAUNCH(adam_dev_kernel, dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev);
+    DPC_LAUNCH((adam_dev_kernel<false>), dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev, (float*)nullptr, (const int32_t*)nullptr, 0.f);
+    return dpc_launch_status();
+}
+
+// dpc_adam_dev_ex plus the parameter average (see ema_weight): ema is one more f32 arena of n floats, 16-byte aligned and not p;
+// step_dev is the device step counter dpc_step_advance[_gated] has already advanced for this step; 0 < decay < 1
+extern "C" int dpc_adam_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
+                                float eps, float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev,
+                                float* ema, const int32_t* step_dev, float decay, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!p || !g || !m || !v || n <= 0 || !bias_corr_dev) return DPC_ERR_ARG;
+    if (!ema || ema == p || !step_dev || !(decay > 0.f && decay < 1.f)) return DPC_ERR_ARG;
+    if (((uintptr_t)p | (uintptr_t)ema) % 16) return DPC_ERR_ARG;
+    const long long n4 = (n + 3) / 4;
+    DPC_LAUNCH((adam_dev_kernel<true>), dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev, ema, step_dev, decay);
     return dpc_launch_status();
 }
 
@@ -457,10 +492,11 @@ extern "C" int dpc_adam(float* p, const float* g, float* m, float* v, int64_t n,
 // tile's start, then every thread advances linearly from there (its units ascend).  A unit outside every segment or inside an
 // inactive one costs no load and no store.  Per-element arithmetic: adam_dev_kernel's.
 constexpr int ADAM_TILE4 = 1024;  // 16-byte units per tile: 4 per thread, 16 KB of each arena
+template <bool EMA>   // the EMA arm: see adam_dev_kernel; a unit the update skips (gap, frozen segment) is skipped in ema too
 __global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float* g, float* m, float* v, long long n4, long long ntiles,
                                                           const dpc_adam_segment* segs, int nseg, float b1, float b2, float omb1,
                                                           float omb2, float eps, const float* bc, float gscale,
-                                                          const dpc_grad_state* gs) {
+                                                          const dpc_grad_state* gs, float* ema, const int32_t* step_dev, float decay) {
     if (gs) {   // as in adam_dev_kernel
         if (gs->skip) return;
         gscale = gscale * gs->coef;
@@ -477,6 +513,8 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float*
     __syncthreads();
     const float bc1 = bc[0];
     const float isb2 = 1.f / sqrtf(bc[1]);
+    float omd = 0.f;
+    if constexpr (EMA) omd = ema_weight(step_dev, decay);
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long t0 = tile * ADAM_TILE4 * 4;   // first float of the tile
         int lo = 0, hi = nseg;                       // first segment with end > t0
@@ -503,6 +541,12 @@ __global__ __launch_bounds__(256) void adam_groups_kernel(float* p, const float*
                 pv[e] -= step * mv[e] / (sqrtf(vv[e]) * isb2 + eps);
             }
             ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+            if constexpr (EMA) {
+                f32x4 ev = ((f32x4*)ema)[i];
+                DPC_UNROLL
+                for (int e = 0; e < 4; ++e) ev[e] += omd * (pv[e] - ev[e]);
+                ((f32x4*)ema)[i] = ev;
+            }
         }
     }
 }
@@ -518,7 +562,23 @@ extern "C" int dpc_adam_groups_dev_ex(float* p, const float* g, float* m, float*
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16) return DPC_ERR_ARG;
     const long long n4 = n / 4, ntiles = (n4 + ADAM_TILE4 - 1) / ADAM_TILE4;
     const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
-    DPC_LAUNCH(adam_groups_kernel, dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev);
+    DPC_LAUNCH((adam_groups_kernel<false>), dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev, (float*)nullptr, (const int32_t*)nullptr, 0.f);
+    return dpc_launch_status();
+}
+
+// dpc_adam_groups_dev_ex plus the parameter average: the arguments dpc_adam_dev_ema adds, with the same requirements
+extern "C" int dpc_adam_groups_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                                       int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
+                                       float grad_scale, const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev,
+                                       float decay, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!p || !g || !m || !v || n <= 0 || n % 4 || !segments_dev || n_segments <= 0 || n_segments > DPC_ADAM_MAX_SEGMENTS || !bias_corr_dev)
+        return DPC_ERR_ARG;
+    if (!ema || ema == p || !step_dev || !(decay > 0.f && decay < 1.f)) return DPC_ERR_ARG;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) % 16) return DPC_ERR_ARG;
+    const long long n4 = n / 4, ntiles = (n4 + ADAM_TILE4 - 1) / ADAM_TILE4;
+    const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
+    DPC_LAUNCH((adam_groups_kernel<true>), dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev, ema, step_dev, decay);
     return dpc_launch_status();
 }
 
@@ -526,4 +586,21 @@ extern "C" int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v,
                                    int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
                                    float grad_scale, dpc_stream_t stream_) {
     return dpc_adam_groups_dev_ex(p, g, m, v, n, segments_dev, n_segments, beta1, beta2, eps, bias_corr_dev, grad_scale, nullptr, stream_);
+}
+
+// ---- exchange two arenas in place, 16 bytes per lane: how evaluation sees the averaged weights while every address a packed table
+// or a captured graph holds stays what it is.  A bit copy (integer lanes): NaN payloads survive.
+__global__ void arena_swap_kernel(u32x4* a, u32x4* b, long long n4) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const u32x4 x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+extern "C" int dpc_arena_swap(float* a, float* b, int64_t n, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!a || !b || a == b || n <= 0 || n % 4 || (((uintptr_t)a | (uintptr_t)b) % 16)) return DPC_ERR_ARG;
+    const long long n4 = n / 4;
+    DPC_LAUNCH(arena_swap_kernel, dim3(grid_for(n4)), dim3(256), stream, (u32x4*)a, (u32x4*)b, n4);
+    return dpc_launch_status();
 }

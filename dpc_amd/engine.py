@@ -539,6 +539,7 @@ class BackboneEngine:
         self._groups, self._groups_key, self._seg_host, self._seg_dev, self._seg_n = None, None, None, None, 0   # parameter groups of the fused Adam (set_param_groups)
         self._guard, self._guard_state, self._guard_partials = None, None, None   # gradient guard of the fused Adam (set_grad_guard)
         self._steps_unsure = False   # a step may have been skipped on the device since _step_count was last read from dev_step
+        self._ema, self.flat_ema, self._ema_swapped = None, None, False   # parameter average of the fused Adam (set_ema, swap_ema)
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -880,6 +881,7 @@ class BackboneEngine:
     # ------------------------------------------------------------------ parameters
     def load_params(self, params: Dict[str, torch.Tensor]):
         """copy a reference-layout state_dict (alias / module. prefixes tolerated) into the flat arena"""
+        self._not_swapped("load_params")
         for k, v in params.items():
             k = k[7:] if k.startswith("module.") else k
             if k.startswith("agg.cell_list.0."):
@@ -890,6 +892,8 @@ class BackboneEngine:
                                f"in PRM: {k in self.PRM}, in shapes: {k in self.shapes})")
             dst.copy_(v.to(torch.float32).reshape(shp))
         self.packed_for_step = -1
+        if self._ema is not None:   # an external write of the parameters restarts their average
+            self.flat_ema.copy_(self.flat_p)
 
     def adopt_optimizer_state(self, old: "BackboneEngine"):
         """continue `old`'s optimisation in this engine (same network, any batch / compute dtype / device): Adam moments, the
@@ -911,9 +915,15 @@ class BackboneEngine:
             self._guard_alloc()
             self._guard_state.copy_(old._guard_state)
             self._guard = old._guard
+        if old.flat_ema is not None:   # the average and its setting
+            old._not_swapped("adopt_optimizer_state")
+            self._ema_alloc()
+            self.flat_ema.copy_(old.flat_ema)
+            self._ema = old._ema
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
+        self._not_swapped("state_dict")
         sd = {k: v.detach().clone() for k, v in self.PRM.items()}
         for k in list(sd):
             if k.startswith("agg.ConvGRUCell_00."):
@@ -1206,14 +1216,108 @@ class BackboneEngine:
         st = L.GradState.from_buffer_copy(self._guard_state.cpu().numpy().tobytes())
         return {"norm": st.norm, "coef": st.coef, "skip": st.skip, "n_skipped": st.n_skipped, "n_clipped": st.n_clipped, "sumsq": st.sumsq}
 
+    # ------------------------------------------------------------------ EMA of the parameters (csrc/loss.hip, the _ema entries)
+    def set_ema(self, decay: Optional[float] = None):
+        """Exponential moving average of the parameters, kept by the fused Adam itself: the thread that has just updated a 16-byte unit
+        of flat_p does ``e += (1 - d) (p_new - e)`` on the same unit of ``flat_ema``, d = min(decay, (1 + t) / (10 + t)) with t the
+        optimizer-step count after this step (the usual warm-up, always on).  No launch, no graph node and no collective of its own:
+        every rank updates the same bits.  A step the gradient guard skips and a frozen parameter leave the average untouched.
+        decay=None (the default) turns it off: adam_step() then launches exactly what it launched without it, and flat_ema -- once
+        allocated -- keeps its values until the average is turned on again.
+
+        ``flat_ema`` is allocated and seeded with a copy of flat_p at the first enabling -- before a step is captured, a captured step
+        allocates nothing.  load_params() re-seeds it while the average is on.  The decay is among the scalars a captured step bakes
+        in: a replay after it changed raises.  Only parameters are averaged: the running buffers of the LC classifier's BatchNorm
+        (``BUF``) are shared between the raw and the averaged model.  Read the average with ema_state_dict(), evaluate with it inside
+        ``with eng.ema_weights():``."""
+        if decay is not None:
+            decay = float(decay)
+            if not 0.0 < decay < 1.0:
+                raise ValueError(f"set_ema: decay must be None or lie in (0, 1), got {decay}")
+            self._not_swapped("set_ema")
+            self._ema_alloc()
+        self._ema = decay
+
+    def _ema_alloc(self):
+        if self.flat_ema is None:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise L.DpcError("set_ema: enable the average before a step is captured (it allocates its arena)")
+            self.flat_ema = self.flat_p.detach().clone()
+
+    @property
+    def ema_decay(self) -> Optional[float]:
+        """the decay, or None while the average is off"""
+        return self._ema
+
+    def _not_swapped(self, what: str):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what}: flat_p holds the averaged weights (swap_ema / ema_weights); swap back first")
+
+    def swap_ema(self):
+        """exchange flat_p and flat_ema in place (dpc_arena_swap: one launch, a bit copy).  ``PRM``, the pack tables and every captured
+        graph keep their addresses and now see the averaged weights; a second call puts everything back, bit for bit.  While the arenas
+        are exchanged only evaluation is allowed: adam_step, train_step, a train-step replay, state_dict(), ema_state_dict() and the
+        checkpoint writers raise.  An eval-step replay repacks inside the graph, so it evaluates whatever is in flat_p."""
+        if self.flat_ema is None:
+            raise RuntimeError("swap_ema: the parameter average was never enabled (set_ema)")
+        self.call("dpc_arena_swap", self.flat_p, self.flat_ema, self.numel)
+        self._ema_swapped = not self._ema_swapped
+        self.packed_for_step = -1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with eng.ema_weights():`` -- forward / evaluate with the averaged parameters (and, for LC, the shared running buffers)"""
+        self._not_swapped("ema_weights")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """state_dict() over flat_ema (alias keys included; running buffers, which are not averaged, as state_dict() gives them).
+        No swap."""
+        if self.flat_ema is None:
+            raise RuntimeError("ema_state_dict: the parameter average was never enabled (set_ema)")
+        sd = self.state_dict()
+        for k, (o, n) in self.offsets.items():
+            sd[k] = self.flat_ema[o:o + n].detach().clone().view(self.shapes[k])
+        for k in sd:
+            if k.startswith("agg.cell_list.0."):
+                sd[k] = sd[k.replace("agg.cell_list.0.", "agg.ConvGRUCell_00.")]
+        return sd
+
     def _count_step(self):
         """one more attempted optimizer step on the host mirror; with skip_nonfinite the device may have counted none"""
         self._step_count += 1
         if self._guard is not None and self._guard[1]:
             self._steps_unsure = True
 
+    def _adam_step_ema(self, grad_scale: float):
+        """adam_step() with the parameter average on: the four arms of adam_step (guard on / off x groups yes / no) through the _ema
+        entries, which take the guard's record as a nullable argument"""
+        st = None
+        seg, nseg = (self._seg_dev, self._seg_n) if self._groups else (None, 0)
+        if self._guard is not None:
+            max_norm, skip_nonfinite = self._guard
+            st = self._guard_state
+            self.call("dpc_grad_sumsq", self.flat_g, self.numel, seg, nseg, self._guard_partials)
+            self.call("dpc_grad_verdict", self._guard_partials, L.GRAD_PARTIALS, max_norm or 0.0, int(skip_nonfinite), st)
+            self.call("dpc_step_advance_gated", self.dev_step, self.dev_bc, 0.9, 0.999, st)
+        else:
+            self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
+        if self._groups:
+            self.call("dpc_adam_groups_dev_ema", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, seg, nseg,
+                      0.9, 0.999, 1e-8, self.dev_bc, grad_scale, st, self.flat_ema, self.dev_step, self._ema)
+        else:
+            self.call("dpc_adam_dev_ema", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
+                      self.wd, self.dev_bc, grad_scale, st, self.flat_ema, self.dev_step, self._ema)
+
     def adam_step(self, grad_scale: float = 1.0):
+        self._not_swapped("adam_step")
         self._count_step()
+        if self._ema is not None:
+            return self._adam_step_ema(grad_scale)
         if self._guard is not None:
             # Runs after the gradient exchange: every rank reduces the same all-reduced arena with the same work split and the same
             # summation order, so all ranks reach the same verdict bit for bit -- no collective, no host.
@@ -1262,7 +1366,10 @@ class BackboneEngine:
         if self._groups:
             base = base + ((self._seg_n, self._seg_host),)
         # ... and with the gradient guard its two settings (only then: the keys of unguarded runs stay what they were)
-        return base + (("grad_guard",) + self._guard,) if self._guard is not None else base
+        if self._guard is not None:
+            base = base + (("grad_guard",) + self._guard,)
+        # ... and with the parameter average its decay (again only then)
+        return base + (("ema", self._ema),) if self._ema is not None else base
 
     def check_graph_capture(self):
         """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
@@ -1332,7 +1439,7 @@ class BackboneEngine:
             if eng is None:
                 raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
             if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
-                raise RuntimeError(f"lr / wd / dropout / gradient guard changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
+                raise RuntimeError(f"lr / wd / dropout / gradient guard / EMA decay changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
                                    f"call {again}")
             return run(eng, graphs)
 
@@ -1407,6 +1514,7 @@ class BackboneEngine:
             self._step_count, self._steps_unsure = host_steps, unsure  # capture executes nothing
 
         def run(eng, graphs):
+            eng._not_swapped("replay of a captured train step")
             graphs[0].replay()
             if two_bucket:
                 allreduce.start(tail)
@@ -1684,6 +1792,7 @@ class DPCEngine(BackboneEngine):
 
     def train_step(self, block: torch.Tensor, dropout_masks: Optional[torch.Tensor] = None, allreduce=None) -> torch.Tensor:
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""
+        self._not_swapped("train_step")
         self._forward_loss(block, True, dropout_masks=dropout_masks)
         self._backward_and_exchange(allreduce)
         self.adam_step()

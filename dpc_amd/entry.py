@@ -6,6 +6,7 @@ sources, schedules and log lines stay in the entries.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -96,6 +97,36 @@ class GuardLog:
         skipped, clipped = now[0] - self.seen[0], now[1] - self.seen[1]
         self.seen = now
         return 'Grad guard: {0} skipped, {1} clipped of {2} steps'.format(skipped, clipped, steps)
+
+
+def add_ema_flags(parser):
+    """--ema / --ema_eval / --use_ema of both entries (BackboneEngine.set_ema)"""
+    parser.add_argument('--ema', default=0.0, type=float, metavar='DECAY', help='keep an exponential moving average of the parameters with '
+                        'this decay inside the fused optimizer step (no extra launch; warm-up min(decay, (1 + t) / (10 + t)); works under '
+                        '--graph and --resident); checkpoints gain an \'ema\' entry.  0 = off')
+    parser.add_argument('--ema_eval', action='store_true', help='validate each epoch with the averaged weights (best-checkpoint selection '
+                        'follows).  Needs --ema')
+    parser.add_argument('--use_ema', action='store_true', help='read the checkpoints given to --pretrain / --test / --retrieval through their '
+                        'averaged weights (the \'ema\' entry; an error when a file has none)')
+
+
+def check_ema_flags(args):
+    """what the entries refuse before they start a rank"""
+    if not 0.0 <= args.ema < 1.0:
+        raise ValueError('--ema must lie in (0, 1) (0 = off)')
+    if args.ema_eval and not args.ema > 0.0:
+        raise ValueError('--ema_eval needs --ema')
+
+
+def open_ema(eng, args, rank: int = 0):
+    """turns the average on from the flags (before any load re-seeds it and before any step is captured) and returns the context
+    the entry validates in: ``eng.ema_weights`` with --ema_eval, else a no-op.  Without --ema nothing is printed"""
+    check_ema_flags(args)
+    if args.ema > 0.0:
+        eng.set_ema(args.ema)
+        if rank == 0:
+            print('EMA: decay {}'.format(args.ema), flush=True)
+    return eng.ema_weights if args.ema_eval else contextlib.nullcontext
 
 
 class StepDriver:

@@ -122,6 +122,7 @@ class LCEngine(BackboneEngine):
                 self.BUF[k2].copy_(v.to(self.BUF[k2].dtype).reshape(self.BUF[k2].shape))
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
+        self._not_swapped("state_dict")
         out = {}
         for k in lc_state_dict_keys(self.network, self.num_class, self.widths):
             if k in self.PRM:
@@ -249,6 +250,7 @@ class LCEngine(BackboneEngine):
     def train_step(self, block: torch.Tensor, target: Optional[torch.Tensor] = None, allreduce=None, **masks) -> torch.Tensor:
         """forward + CE / accuracy + backward (+ gradient all-reduce) + Adam; returns device f32[2] = loss, top-1.
         target=None: the labels as they stand in ``self.target``"""
+        self._not_swapped("train_step")
         self.forward(block, target, train=True, **masks)
         self._backward_and_exchange(allreduce)
         self.adam_step()

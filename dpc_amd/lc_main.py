@@ -66,7 +66,7 @@ import time
 
 import torch
 
-from .entry import GuardLog, StepDriver, average_over_ranks, add_guard_flags, launch, open_rank, world_size
+from .entry import GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, check_ema_flags, launch, open_ema, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -136,6 +136,7 @@ def build_parser() -> argparse.ArgumentParser:
                         'running = eval mode, right for any checkpoint of this entry; batch = the statistics of each chunk of '
                         'windows, for a DPC checkpoint, which carries no running statistics (an embedding then depends on its chunk)')
     add_guard_flags(parser)
+    add_ema_flags(parser)
     return parser
 
 
@@ -286,6 +287,8 @@ def _worker(rank: int, world: int, args, port: int):
     # the gradient guard is on before the first capture and stays on: its settings are among the baked values, so the captures
     # set_lr asks for after a milestone carry it too
     guard = GuardLog.open(eng, args)
+    # the parameter average likewise, and before the loads below: each load re-seeds it, --resume then reads the file's own
+    ema_eval = open_ema(eng, args, rank)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def set_lr(mult, saved=None):
@@ -307,6 +310,8 @@ def _worker(rank: int, world: int, args, port: int):
             log("=> no checkpoint found at '{}'".format(path))
             continue
         ck = torch.load(path, map_location='cpu', weights_only=False)
+        if args.use_ema and what != 'resume':   # --use_ema: the parameters of the file's averaged model, the buffers of its own
+            ck['state_dict'] = ckpt.averaged_state_dict(eng, ck, path)
         # --resume: nn.Module.load_state_dict, strict in both directions (eval/test.py:145); --test: strict, falling back to the
         # key intersection with a warning (:113-116); --pretrain: key intersection (neq_load_customized, :160)
         try:
@@ -323,6 +328,7 @@ def _worker(rank: int, world: int, args, port: int):
             args.start_epoch = ck['epoch']
             best_acc = float(ck.get('best_acc', 0.0))
             iteration = int(ck.get('iteration', 0))
+            ckpt.load_ema_state(eng, ck, path)
             if not args.reset_lr and 'optimizer' in ck:
                 if groups is None:
                     ckpt.load_optimizer_state(eng, ck['optimizer'])  # restores the group's lr as optimizer.load_state_dict does
@@ -460,10 +466,11 @@ def _worker(rank: int, world: int, args, port: int):
             feed = src_val.epoch(dev) if src_val is not None and not args.resident else None
             if args.resident:
                 src_val.begin_epoch()
-            for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
-                loss, acc = reduce(step(False, feed))
-                vl += loss
-                va += acc
+            with ema_eval():   # --ema_eval: the averaged weights are swapped into flat_p for the validation epoch
+                for idx in range(n_val):  # validate(): eval/test.py:273-304 (eval mode, running statistics)
+                    loss, acc = reduce(step(False, feed))
+                    vl += loss
+                    va += acc
             nv = max(n_val, 1)
             val_acc = va / nv
             log('Loss {:.4f}\t Acc: {:.4f} \t'.format(vl / nv, val_acc), flush=True)
@@ -476,11 +483,14 @@ def _worker(rank: int, world: int, args, port: int):
                          'best_acc': best_acc, 'iteration': iteration,
                          'optimizer': (ckpt.optimizer_state_dict(eng) if groups is None else
                                        ckpt.grouped_optimizer_state_dict(eng, [g for g in eng.param_groups if not g['frozen']]))}
+                if eng.ema_decay is not None:
+                    state['ema'] = ckpt.ema_entry(eng, state['state_dict'])
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
         log('Training from ep %d to ep %d finished' % (args.start_epoch, args.epochs))
         if probe:
             torch.save({'flat_p': eng.flat_p.detach().cpu(), 'flat_m': eng.flat_m.detach().cpu(), 'step': eng.step_count, 'rank': rank,
-                        'world': world, 'per_gpu': per_gpu}, os.path.join(probe, f'rank{rank}.pt'))
+                        'world': world, 'per_gpu': per_gpu, **({'flat_ema': eng.flat_ema.detach().cpu()} if eng.ema_decay is not None else {})},
+                       os.path.join(probe, f'rank{rank}.pt'))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -489,6 +499,7 @@ def _worker(rank: int, world: int, args, port: int):
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
+    check_ema_flags(args)
     world = world_size(args)
     if args.resident and not args.frames:
         raise ValueError('--resident holds the --frames array in HBM: --frames is missing')

@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from .entry import GuardLog, StepDriver, average_over_ranks, add_guard_flags, launch, open_rank, world_size
+from .entry import GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, check_ema_flags, launch, open_ema, open_rank, world_size
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -76,6 +76,7 @@ def build_parser() -> argparse.ArgumentParser:
                         '[total_frames, H0, W0, 3] of videos of any length, video v = frames[offsets[v]:offsets[v + 1]].  Needs --resident')
     parser.add_argument('--val_offsets', default='', type=str, help='--offsets of the --val_frames array')
     add_guard_flags(parser)
+    add_ema_flags(parser)
     return parser
 
 
@@ -129,6 +130,7 @@ def _worker(rank: int, world: int, args, port: int):
     init = DPC_RNN(args.img_dim, args.num_seq, args.seq_len, args.pred_step, args.net, widths=widths, seed=0)  # same on every rank
     eng.load_params({k: v.detach() for k, v in init.named_parameters()})
     best_acc, iteration = 0.0, 0
+    ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -144,7 +146,7 @@ def _worker(rank: int, world: int, args, port: int):
             print("[Warning] no checkpoint found at '{}'".format(args.resume))
     if args.pretrain:  # dpc/main.py:104-112: key intersection (neq_load_customized)
         if os.path.isfile(args.pretrain):
-            info = ckpt.pretrain(eng, args.pretrain, log=print if rank == 0 else (lambda *a: None))
+            info = ckpt.pretrain(eng, args.pretrain, log=print if rank == 0 else (lambda *a: None), use_ema=args.use_ema)
             if rank == 0:
                 print("=> loaded pretrained checkpoint '{}' (epoch {})".format(args.pretrain, info['epoch']))
         elif rank == 0:
@@ -232,7 +234,8 @@ def _worker(rank: int, world: int, args, port: int):
 
     for epoch in range(args.start_epoch, args.epochs):
         run_epoch(True, epoch)
-        val_loss, val_acc, val_list = run_epoch(False, epoch)
+        with ema_eval():   # --ema_eval: the averaged weights are swapped into flat_p for the validation epoch
+            val_loss, val_acc, val_list = run_epoch(False, epoch)
         if rank == 0:
             print('[{0}/{1}] Loss {2:.4f}\t Acc: top1 {3:.4f}; top3 {4:.4f}; top5 {5:.4f} \t'.format(epoch, args.epochs, val_loss, *val_list), flush=True)
             if args.save_dir:
@@ -248,7 +251,8 @@ def _worker(rank: int, world: int, args, port: int):
     probe = getattr(args, '_probe', None)   # tests only: every rank leaves its parameter arena behind (identical on all ranks by construction)
     if probe:
         torch.save({'flat_p': eng.flat_p.detach().cpu(), 'flat_m': eng.flat_m.detach().cpu(), 'step': eng.step_count,
-                    'rank': rank, 'world': world, 'per_gpu': per_gpu, 'seed': eng.seed}, os.path.join(probe, f'rank{rank}.pt'))
+                    'rank': rank, 'world': world, 'per_gpu': per_gpu, 'seed': eng.seed,
+                    **({'flat_ema': eng.flat_ema.detach().cpu()} if eng.ema_decay is not None else {})}, os.path.join(probe, f'rank{rank}.pt'))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
@@ -257,6 +261,7 @@ def _worker(rank: int, world: int, args, port: int):
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
+    check_ema_flags(args)
     if args.resident and not args.frames:
         raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')
     if _simulator is not None and world_size(args) != 1:

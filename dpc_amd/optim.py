@@ -29,6 +29,10 @@ Gradient guard: ``Adam(..., max_grad_norm=1.0, skip_nonfinite=True)`` clips the 
 and drops a step whose gradient holds an Inf or NaN, inside the fused step on the device (``BackboneEngine.set_grad_guard``; the
 ``.grad`` tensors are not rewritten).  ``clip_grad_norm_(parameters, max_norm)`` is ``torch.nn.utils.clip_grad_norm_`` over the
 arena: three launches whatever the number of parameters, the norm returned as a device tensor.
+
+Parameter average: ``Adam(..., ema_decay=0.999)`` keeps an exponential moving average of the parameters inside the same fused step
+(``BackboneEngine.set_ema``); ``with ema_weights(optimizer):`` shows the averaged values through ``model.parameters()`` for
+evaluation and puts the trained ones back on exit.
 """
 from __future__ import annotations
 
@@ -43,7 +47,7 @@ from .engine import engine_of
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False,
-                 max_grad_norm=None, skip_nonfinite: bool = False):
+                 max_grad_norm=None, skip_nonfinite: bool = False, ema_decay=None):
         if amsgrad:
             raise ValueError("amsgrad is not supported (the reference does not use it, dpc/main.py:80-81)")
         if tuple(betas) != (0.9, 0.999) or eps != 1e-8:
@@ -59,6 +63,9 @@ class Adam(torch.optim.Optimizer):
         if max_grad_norm is not None and not (0.0 < float(max_grad_norm) < float("inf")):
             raise ValueError(f"max_grad_norm must be None or a finite positive number, got {max_grad_norm}")
         self._guard = (max_grad_norm, bool(skip_nonfinite))   # (None, False): the engine's guard is left as it is
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be None or lie in (0, 1), got {ema_decay}")
+        self._ema = ema_decay   # None: the engine's average is left as it is
         self._pending_state = None
         self._by_ptr = None     # (engine, {arena address: parameter name})
         self._updated = set()   # names of the parameters that have been updated at least once (torch creates their state then)
@@ -115,6 +122,8 @@ class Adam(torch.optim.Optimizer):
                                   for g, have in zip(self.param_groups, live)])
         if self._guard != (None, False):
             eng.set_grad_guard(*self._guard)
+        if self._ema is not None and eng.ema_decay != float(self._ema):
+            eng.set_ema(self._ema)
         eng.adam_step()
         self._updated.update(k for have in live for k in have)
         eng.packed_for_step = -1
@@ -154,6 +163,13 @@ class Adam(torch.optim.Optimizer):
             self._pending_state = state_dict   # the engine does not exist yet: applied at the first step
             return
         self._load_into(eng, names, state_dict)
+
+
+def ema_weights(optimizer: Adam):
+    """``with ema_weights(optimizer):`` -- inside, the parameters the optimizer updates (views of the engine's arena) hold their
+    averaged values; on exit the trained values are back, bit for bit.  Evaluation only: a step inside the block raises."""
+    eng, _ = optimizer._engine()
+    return eng.ema_weights()
 
 
 def _arena_names(params, who: str):

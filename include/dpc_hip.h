@@ -372,6 +372,24 @@ int dpc_adam_groups_dev_ex(float* p, const float* g, float* m, float* v, int64_t
                            const dpc_grad_state* state_dev, dpc_stream_t stream);
 int dpc_grad_scale(float* g, int64_t n, const dpc_adam_segment* segments_dev, int32_t n_segments, const dpc_grad_state* state_dev,
                    dpc_stream_t stream);
+/* ---- EMA of the parameters inside the fused step (csrc/loss.hip): dpc_adam_dev_ex / dpc_adam_groups_dev_ex (state_dev nullable, as
+ * there) with one more f32 arena, `ema`, updated by the thread that has just updated the 16-byte unit of p:
+ *     e += (1 - d) * (p_new - e),   d = min(decay, (float)(1 + t) / (float)(10 + t)),   t = step_dev[0]
+ * in f32 throughout (1 - d included).  t is the optimizer-step count AFTER this step's advance (dpc_step_advance[_gated] runs first);
+ * the warm-up term is always on: without it a decay of 0.999 reports the initial weights for thousands of steps.  The lerp form has
+ * e == p as a fixed point bit for bit.  p, m, v get the bits the _ex entries give them.  Nothing of ema is loaded or stored where
+ * the update loads and stores nothing: a skipped step (state_dev->skip), an inactive segment, a gap of the segment table.
+ * ema: non-null, 16-byte aligned, not p; step_dev non-null; 0 < decay < 1; else DPC_ERR_ARG.  No launch beside the update's own.
+ *   arena_swap   exchanges a[0..n) and b[0..n) in place, 16 bytes per lane, as bits (NaN payloads survive): how evaluation sees the
+ *                averaged weights while every pointer into the parameter arena -- views, pack tables, captured graphs -- stays valid.
+ *                n % 4 == 0, both 16-byte aligned, a != b.  Capturable. */
+int dpc_adam_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+                     float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev, float* ema,
+                     const int32_t* step_dev, float decay, dpc_stream_t stream);
+int dpc_adam_groups_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                            int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
+                            const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev, float decay, dpc_stream_t stream);
+int dpc_arena_swap(float* a, float* b, int64_t n, dpc_stream_t stream);
 /* counter_dev[0] += 1 on the stream: the dropout draw counter (one draw per train-mode forward; the `step_dev` the recurrence and
  * the classifier head key their Philox masks on), graph-capturable like dpc_step_advance */
 int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream);
