@@ -124,6 +124,23 @@ def relerr(a, b):
     return (a.float().cpu() - b.float()).abs().max().item() / max(b.abs().max().item(), 1e-6)
 
 
+def row_offdiag_relerr(got, want, chunk=1024):
+    """per row of a [rows, cols] gradient with its target on the diagonal: max-abs error over the OFF-diagonal elements relative to
+    that row's largest off-diagonal reference element -- relerr's bound, one number per row instead of one per tensor (the tensor's
+    max-abs is a diagonal element, ~1/rows: under it every small off-diagonal element may be anything).  Returns the worst row's."""
+    rows = want.shape[0]
+    worst = 0.0
+    for r0 in range(0, rows, chunk):
+        w = want[r0:r0 + chunk].float()
+        e = (got[r0:r0 + chunk].float().cpu() - w).abs()
+        w = w.abs()
+        i = torch.arange(w.shape[0])
+        e[i, r0 + i] = 0
+        w[i, r0 + i] = 0
+        worst = max(worst, (e.amax(1) / w.amax(1).clamp_min(1e-30)).max().item())
+    return worst
+
+
 class K:
     """binds a Lib + device"""
 
@@ -725,6 +742,8 @@ def case_ce_topk(k: K, rows, cols, dtype_d, seed=10):
     assert abs(r[0].item() - loss.item()) < 1e-5 * max(1.0, abs(loss.item()))
     assert [round(v, 6) for v in r[1:].tolist()] == [round(v, 6) for v in accs]
     assert relerr(ds[:, :cols], sd.grad) < tol(dtype_d)
+    assert row_offdiag_relerr(ds[:, :cols], sd.grad) < tol(dtype_d)   # the same bound, per row (tests/loss_cases.py holds every element)
+    assert torch.equal(ws[:, 1].cpu().double(), (s > s.diagonal()[:, None]).sum(1).double())   # random f32 data: no ties
     if ld_d > cols:
         assert ds[:, cols:].float().abs().max().item() == 0
 
@@ -1249,6 +1268,8 @@ def case_ce_topk_bf16(k: K, rows, cols, seed=10):
     assert abs(r[0].item() - loss.item()) < 2e-5 * max(1.0, abs(loss.item()))
     assert [round(v, 6) for v in r[1:].tolist()] == [round(v, 6) for v in accs]
     assert relerr(ds[:, :cols], sd.grad) < tol(torch.bfloat16)
+    assert row_offdiag_relerr(ds[:, :cols], sd.grad) < tol(torch.bfloat16)   # the same bound, per row
+    assert torch.equal(ws[:, 1].cpu().double(), rank.double())               # strictly greater among the rounded values
 
 
 def case_gemm_nt_bf16out(k: K, M, N, Kd, seed=3, expect="score_gemm2_kernel<KS,OUT16>"):
