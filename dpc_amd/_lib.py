@@ -73,6 +73,20 @@ class GradState(C.Structure):
 
 GRAD_PARTIALS = 1024   # DPC_GRAD_PARTIALS
 
+LR_CONSTANT, LR_COSINE, LR_LINEAR, LR_MULTISTEP = 0, 1, 2, 3   # DPC_LR_* (include/dpc_hip.h)
+LR_MAX_MILESTONES = 8   # DPC_LR_MAX_MILESTONES
+
+
+class LrSchedule(C.Structure):
+    """struct dpc_lr_schedule (include/dpc_hip.h): host memory, passed to the kernel by value"""
+    _fields_ = [("kind", C.c_int32), ("warmup_steps", C.c_int32), ("total_steps", C.c_int32), ("n_milestones", C.c_int32),
+                ("min_mult", C.c_double), ("gamma", C.c_double), ("milestones", C.c_int32 * LR_MAX_MILESTONES)]
+
+
+class LrState(C.Structure):
+    """struct dpc_lr_state (include/dpc_hip.h): the multiplier of the last step taken, in device memory"""
+    _fields_ = [("mult", C.c_float), ("k", C.c_int32), ("reserved", C.c_int32 * 2)]
+
 
 class ConvEpilogue(C.Structure):
     """struct dpc_conv_epilogue (include/dpc_hip.h)"""
@@ -166,6 +180,9 @@ _SIGS = {
     "dpc_adam_dev_ema": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
     "dpc_adam_groups_dev_ema": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
     "dpc_arena_swap": [_vp, _vp, _i64, _vp],
+    "dpc_step_advance_sched": [_vp, _vp, _f64, _f64, _vp, C.POINTER(LrSchedule), _vp, _vp],
+    "dpc_adam_dev_sched": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
+    "dpc_adam_groups_dev_sched": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
     "dpc_counter_advance": [_vp, _vp],
     "dpc_copy2d_f32": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "dpc_copy2d_multi": [_vp, _i32, _i32, _vp],

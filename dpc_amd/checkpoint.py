@@ -173,12 +173,31 @@ def ema_entry(eng, keys: Iterable[str]) -> dict:
     return {"decay": float(eng.ema_decay), "state_dict": {k: av[_strip(k)].cpu() for k in keys}}
 
 
+def lr_schedule_entry(eng) -> dict:
+    """the checkpoint's top-level 'lr_schedule' entry while the engine steps by a schedule (BackboneEngine.set_lr_schedule): the
+    schedule's own fields.  The optimizer's 'lr' stays the base value and the multiplier is a function of the step count the optimizer
+    state already holds, so the reference resumes the file as before and nothing else needs storing."""
+    return eng.lr_schedule.to_dict()
+
+
+def check_lr_schedule(eng, ck: dict, path: str) -> None:
+    """a resumed run takes its schedule from the flags or the caller, never from the file; one warning if the file was written under
+    another one (or the run has none).  A file without the entry says nothing."""
+    if "lr_schedule" not in ck:
+        return
+    mine = eng.lr_schedule.to_dict() if eng.lr_schedule is not None else None
+    if mine != ck["lr_schedule"]:
+        warnings.warn(f"{path} was written under the learning-rate schedule {ck['lr_schedule']}, this run continues with {mine}")
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
-    """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the parameter
-    average on, plus 'ema' (ema_entry)"""
+    """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
+    schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry)"""
     eng._not_swapped("build_state")
     state = {"epoch": epoch, "net": net, "state_dict": model_state_dict(eng), "best_acc": best_acc,
              "optimizer": optimizer_state_dict(eng), "iteration": iteration}
+    if eng.lr_schedule is not None:
+        state["lr_schedule"] = lr_schedule_entry(eng)
     if eng.ema_decay is not None:
         state["ema"] = ema_entry(eng, state["state_dict"])
     return state
@@ -225,9 +244,11 @@ def save_checkpoint(state: dict, is_best: bool = False, gap: int = 1, filename: 
         torch.save(state, os.path.join(d, "model_best_epoch%s.pth.tar" % str(state["epoch"])))
 
 
-def resume(eng, path: str, reset_lr: bool = False) -> dict:
+def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) -> dict:
     """--resume (dpc/main.py:88-102): strict model load, optimizer state unless reset_lr.  Returns the bookkeeping
-    fields {'epoch', 'iteration', 'best_acc'}."""
+    fields {'epoch', 'iteration', 'best_acc'}, plus the file's 'lr_schedule' entry when it has one.  The learning-rate schedule is not
+    read from the file: the engine's own is compared with it (check_lr_schedule) -- unless check_schedule is False, for a caller
+    that sets its schedule only after the load and compares then."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
     load_model_state(eng, ck["state_dict"], strict=True)
     if not reset_lr:
@@ -241,7 +262,12 @@ def resume(eng, path: str, reset_lr: bool = False) -> dict:
         else:
             warnings.warn(f"{path} holds no optimizer state: Adam moments and step count start from zero")
     load_ema_state(eng, ck, path)
-    return {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}
+    if check_schedule:
+        check_lr_schedule(eng, ck, path)
+    info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}
+    if "lr_schedule" in ck:
+        info["lr_schedule"] = ck["lr_schedule"]
+    return info
 
 
 def pretrain(eng, path: str, log=print, use_ema: bool = False) -> dict:

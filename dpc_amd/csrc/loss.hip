@@ -378,6 +378,63 @@ extern "C" int dpc_step_advance(int32_t* step_dev, float* bias_corr_dev, double 
     return dpc_launch_status();
 }
 
+// ---- per-step learning-rate schedule (include/dpc_hip.h: dpc_lr_schedule): the multiplier of the step about to be taken, formed by
+// the one thread that advances the counter and read by the Adam kernel of the same step -- no launch of its own.  k is the count of
+// completed optimizer steps, so a step the guard skips does not move the schedule and a resumed run continues it from dev_step.
+// Double throughout, no contraction: the host statement (dpc_amd/optim.py: lr_multiplier) performs the same roundings one by one.
+__device__ __forceinline__ double lr_mult(const dpc_lr_schedule& s, int k) {
+#pragma clang fp contract(off)
+    const int W = s.warmup_steps;
+    if (k < W) return (double)(k + 1) / (double)W;
+    if (s.kind == DPC_LR_COSINE || s.kind == DPC_LR_LINEAR) {
+        const double m0 = s.min_mult;
+        const double x = (double)(k - W) / (double)(s.total_steps - W);
+        if (x >= 1.0) return m0;
+        const double shape = s.kind == DPC_LR_COSINE ? 0.5 * (1.0 + cos(3.141592653589793 * x)) : 1.0 - x;
+        return m0 + (1.0 - m0) * shape;
+    }
+    double mult = 1.0;
+    if (s.kind == DPC_LR_MULTISTEP)
+        for (int i = 0; i < s.n_milestones; ++i)
+            if (s.milestones[i] <= k) mult *= s.gamma;
+    return mult;
+}
+
+__global__ void step_advance_sched_kernel(int32_t* step, float* bc, double b1, double b2, const dpc_grad_state* st, dpc_lr_schedule sched,
+                                          dpc_lr_state* lrs) {
+    if (threadIdx.x == 0 && blockIdx.x == 0 && !(st && st->skip)) {
+        const int k = step[0], t = k + 1;
+        step[0] = t;
+        bc[0] = (float)(1.0 - pow(b1, (double)t));
+        bc[1] = (float)(1.0 - pow(b2, (double)t));
+        lrs->mult = (float)lr_mult(sched, k);
+        lrs->k = k;
+    }
+}
+
+static bool lr_schedule_ok(const dpc_lr_schedule* s) {
+    if (!s || s->kind < DPC_LR_CONSTANT || s->kind > DPC_LR_MULTISTEP || s->warmup_steps < 0) return false;
+    if (s->kind == DPC_LR_COSINE || s->kind == DPC_LR_LINEAR) {
+        if (!(s->total_steps > s->warmup_steps) || !(s->min_mult >= 0.0 && s->min_mult <= 1.0)) return false;
+    }
+    if (s->kind == DPC_LR_MULTISTEP) {
+        if (s->n_milestones < 0 || s->n_milestones > DPC_LR_MAX_MILESTONES || !(s->gamma > 0.0 && s->gamma <= 1.0)) return false;
+        for (int i = 0; i < s->n_milestones; ++i)
+            if (s->milestones[i] < 0 || (i && s->milestones[i] <= s->milestones[i - 1])) return false;
+    }
+    return true;
+}
+
+// state_dev: the gradient guard's verdict (dpc_step_advance_gated), or null (dpc_step_advance)
+extern "C" int dpc_step_advance_sched(int32_t* step_dev, float* bias_corr_dev, double beta1, double beta2, const dpc_grad_state* state_dev,
+                                      const dpc_lr_schedule* schedule, dpc_lr_state* lr_state_dev, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!step_dev || !bias_corr_dev || !lr_state_dev || (uintptr_t)lr_state_dev % 4 || !lr_schedule_ok(schedule)) return DPC_ERR_ARG;
+    const dpc_lr_schedule by_value = *schedule;
+    DPC_LAUNCH(step_advance_sched_kernel, dim3(1), dim3(64), stream, step_dev, bias_corr_dev, beta1, beta2, state_dev, by_value, lr_state_dev);
+    return dpc_launch_status();
+}
+
 // draw counter of the dropout streams: advanced by every train-mode forward (not by the optimizer step), so a caller that never
 // runs the engine's own Adam -- the nn.Module boundary with a torch optimizer -- still sees fresh masks each forward
 __global__ void counter_advance_kernel(int32_t* ctr) {
@@ -586,6 +643,154 @@ extern "C" int dpc_adam_groups_dev(float* p, const float* g, float* m, float* v,
                                    int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
                                    float grad_scale, dpc_stream_t stream_) {
     return dpc_adam_groups_dev_ex(p, g, m, v, n, segments_dev, n_segments, beta1, beta2, eps, bias_corr_dev, grad_scale, nullptr, stream_);
+}
+
+// ---- the scheduled arm of both updates (dpc_adam_dev_sched / dpc_adam_groups_dev_sched): adam_dev_kernel and adam_groups_kernel with
+// the step size (lr * lrs->mult) / bc1, lrs the record step_advance_sched_kernel has just written -- the f32 product first.  Kernels of
+// their own, so that every older entry launches the kernel, with the argument list, it always launched; the bodies are those kernels'
+// line for line except where marked, and tests/lr_schedule_cases.py holds mult = 1 to their bits.
+template <bool EMA>
+__global__ void adam_dev_sched_kernel(float* p, const float* g, float* m, float* v, long long n4, long long n, float lr, float b1,
+                                float b2, float omb1, float omb2, float eps, float wd, const float* bc, float gscale,
+                                const dpc_grad_state* gs, float* ema, const int32_t* step_dev, float decay, const dpc_lr_state* lrs) {
+    if (gs) {   // the gradient guard's verdict (grad_guard.hip): a skipped step loads and stores nothing
+        if (gs->skip) return;
+        gscale = gscale * gs->coef;
+    }
+    const float step = (lr * lrs->mult) / bc[0];   // the f32 product first, then the division adam_dev_kernel performs
+    const float isb2 = 1.f / sqrtf(bc[1]);
+    float omd = 0.f;
+    if constexpr (EMA) omd = ema_weight(step_dev, decay);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+        const long long base = i * 4;
+        if (base + 4 <= n) {
+            f32x4 pv = ((f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+            DPC_UNROLL
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * gscale + wd * pv[e];
+                mv[e] = b1 * mv[e] + omb1 * gg;
+                vv[e] = b2 * vv[e] + omb2 * gg * gg;
+                pv[e] -= step * mv[e] / (sqrtf(vv[e]) * isb2 + eps);
+            }
+            ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+            if constexpr (EMA) {
+                f32x4 ev = ((f32x4*)ema)[i];
+                DPC_UNROLL
+                for (int e = 0; e < 4; ++e) ev[e] += omd * (pv[e] - ev[e]);
+                ((f32x4*)ema)[i] = ev;
+            }
+        } else {
+            for (long long k = base; k < n; ++k) {
+                const float gg = g[k] * gscale + wd * p[k];
+                m[k] = b1 * m[k] + omb1 * gg;
+                v[k] = b2 * v[k] + omb2 * gg * gg;
+                p[k] -= step * m[k] / (sqrtf(v[k]) * isb2 + eps);
+                if constexpr (EMA) ema[k] += omd * (p[k] - ema[k]);
+            }
+        }
+    }
+}
+
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_groups_sched_kernel(float* p, const float* g, float* m, float* v, long long n4, long long ntiles,
+                                                          const dpc_adam_segment* segs, int nseg, float b1, float b2, float omb1,
+                                                          float omb2, float eps, const float* bc, float gscale,
+                                                          const dpc_grad_state* gs, float* ema, const int32_t* step_dev, float decay, const dpc_lr_state* lrs) {
+    if (gs) {   // as in adam_dev_kernel
+        if (gs->skip) return;
+        gscale = gscale * gs->coef;
+    }
+    __shared__ long long s_begin[DPC_ADAM_MAX_SEGMENTS], s_end[DPC_ADAM_MAX_SEGMENTS];
+    __shared__ float s_lr[DPC_ADAM_MAX_SEGMENTS], s_wd[DPC_ADAM_MAX_SEGMENTS];   // lr < 0 marks an inactive segment
+    const int tid = threadIdx.x;
+    const float mult = lrs->mult;   // uniform
+    for (int s = tid; s < nseg; s += 256) {
+        s_begin[s] = segs[s].begin;
+        s_end[s] = segs[s].end;
+        s_lr[s] = segs[s].active ? segs[s].lr * mult : -1.f;   // lr, mult >= 0: the product never reads as inactive
+        s_wd[s] = segs[s].weight_decay;
+    }
+    __syncthreads();
+    const float bc1 = bc[0];
+    const float isb2 = 1.f / sqrtf(bc[1]);
+    float omd = 0.f;
+    if constexpr (EMA) omd = ema_weight(step_dev, decay);
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long t0 = tile * ADAM_TILE4 * 4;   // first float of the tile
+        int lo = 0, hi = nseg;                       // first segment with end > t0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (s_end[mid] <= t0) lo = mid + 1; else hi = mid;
+        }
+        int s = lo;
+        DPC_UNROLL
+        for (int j = 0; j < ADAM_TILE4 / 256; ++j) {
+            const long long i = tile * ADAM_TILE4 + tid + 256 * j;
+            const long long base = i * 4;
+            if (i >= n4) break;
+            while (s < nseg && s_end[s] <= base) ++s;
+            if (s >= nseg) break;
+            if (s_begin[s] > base || s_lr[s] < 0.f) continue;   // padding between segments, or frozen
+            const float step = s_lr[s] / bc1, wd = s_wd[s];
+            f32x4 pv = ((f32x4*)p)[i], gv = ((const f32x4*)g)[i], mv = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+            DPC_UNROLL
+            for (int e = 0; e < 4; ++e) {
+                const float gg = gv[e] * gscale + wd * pv[e];
+                mv[e] = b1 * mv[e] + omb1 * gg;
+                vv[e] = b2 * vv[e] + omb2 * gg * gg;
+                pv[e] -= step * mv[e] / (sqrtf(vv[e]) * isb2 + eps);
+            }
+            ((f32x4*)p)[i] = pv; ((f32x4*)m)[i] = mv; ((f32x4*)v)[i] = vv;
+            if constexpr (EMA) {
+                f32x4 ev = ((f32x4*)ema)[i];
+                DPC_UNROLL
+                for (int e = 0; e < 4; ++e) ev[e] += omd * (pv[e] - ev[e]);
+                ((f32x4*)ema)[i] = ev;
+            }
+        }
+    }
+}
+
+
+// The entries: the _ema entries' arguments plus the record.  The average is optional here (ema and step_dev both null: the <false>
+// kernels), so one entry serves guard x EMA.
+static inline bool sched_ema_ok(const float* p, const float* ema, const int32_t* step_dev, float decay) {
+    if (!ema) return !step_dev;
+    return ema != p && step_dev && decay > 0.f && decay < 1.f && ((uintptr_t)p | (uintptr_t)ema) % 16 == 0;
+}
+
+extern "C" int dpc_adam_dev_sched(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2,
+                                  float eps, float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev,
+                                  float* ema, const int32_t* step_dev, float decay, const dpc_lr_state* lr_state_dev,
+                                  dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!p || !g || !m || !v || n <= 0 || !bias_corr_dev || !lr_state_dev || (uintptr_t)lr_state_dev % 4) return DPC_ERR_ARG;
+    if (!sched_ema_ok(p, ema, step_dev, decay)) return DPC_ERR_ARG;
+    const long long n4 = (n + 3) / 4;
+    if (ema)
+        DPC_LAUNCH((adam_dev_sched_kernel<true>), dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev, ema, step_dev, decay, lr_state_dev);
+    else
+        DPC_LAUNCH((adam_dev_sched_kernel<false>), dim3(grid_for(n4)), dim3(256), stream, p, g, m, v, n4, (long long)n, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bias_corr_dev, grad_scale, state_dev, (float*)nullptr, (const int32_t*)nullptr, 0.f, lr_state_dev);
+    return dpc_launch_status();
+}
+
+extern "C" int dpc_adam_groups_dev_sched(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                                         int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev,
+                                         float grad_scale, const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev,
+                                         float decay, const dpc_lr_state* lr_state_dev, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!p || !g || !m || !v || n <= 0 || n % 4 || !segments_dev || n_segments <= 0 || n_segments > DPC_ADAM_MAX_SEGMENTS || !bias_corr_dev)
+        return DPC_ERR_ARG;
+    if (!lr_state_dev || (uintptr_t)lr_state_dev % 4 || !sched_ema_ok(p, ema, step_dev, decay)) return DPC_ERR_ARG;
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16) return DPC_ERR_ARG;
+    const long long n4 = n / 4, ntiles = (n4 + ADAM_TILE4 - 1) / ADAM_TILE4;
+    const unsigned grid = (unsigned)(ntiles < 2048 ? ntiles : 2048);
+    if (ema)
+        DPC_LAUNCH((adam_groups_sched_kernel<true>), dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev, ema, step_dev, decay, lr_state_dev);
+    else
+        DPC_LAUNCH((adam_groups_sched_kernel<false>), dim3(grid), dim3(256), stream, p, g, m, v, n4, ntiles, segments_dev, (int)n_segments, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, bias_corr_dev, grad_scale, state_dev, (float*)nullptr, (const int32_t*)nullptr, 0.f, lr_state_dev);
+    return dpc_launch_status();
 }
 
 // ---- exchange two arenas in place, 16 bytes per lane: how evaluation sees the averaged weights while every address a packed table

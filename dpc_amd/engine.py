@@ -540,6 +540,7 @@ class BackboneEngine:
         self._guard, self._guard_state, self._guard_partials = None, None, None   # gradient guard of the fused Adam (set_grad_guard)
         self._steps_unsure = False   # a step may have been skipped on the device since _step_count was last read from dev_step
         self._ema, self.flat_ema, self._ema_swapped = None, None, False   # parameter average of the fused Adam (set_ema, swap_ema)
+        self._lr_sched, self._lr_desc, self._lr_state = None, None, None   # per-step learning-rate schedule of the fused Adam (set_lr_schedule)
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -920,6 +921,10 @@ class BackboneEngine:
             self._ema_alloc()
             self.flat_ema.copy_(old.flat_ema)
             self._ema = old._ema
+        if old._lr_desc is not None:   # the schedule and the record of its last step
+            self._lr_alloc()
+            self._lr_state.copy_(old._lr_state)
+            self._lr_sched, self._lr_desc = old._lr_sched, old._lr_desc
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1287,6 +1292,70 @@ class BackboneEngine:
                 sd[k] = sd[k.replace("agg.cell_list.0.", "agg.ConvGRUCell_00.")]
         return sd
 
+    # ------------------------------------------------------------------ per-step learning-rate schedule (csrc/loss.hip, the _sched entries)
+    def set_lr_schedule(self, schedule=None):
+        """Learning-rate multiplier evaluated on the device, once per optimizer step, by the thread that advances the step counter
+        (dpc_step_advance_sched) and read by the update of the same step: every parameter group steps with ``lr_group * mult(k)``,
+        k = completed optimizer steps (dev_step before the advance).  schedule: a dpc_amd.optim.LRSchedule (warm-up, then constant /
+        cosine / linear / multistep; optim.lr_multiplier is the same function on the host), or None (the default) to turn it off:
+        adam_step() then launches exactly what it launched without it.  ``self.lr`` and the groups' lrs stay the BASE values.
+
+        No launch, graph node, collective or host work per step is added, so it works in a replayed step; every rank evaluates the
+        same function of the same count.  A step the gradient guard skips does not advance the schedule; a resumed run continues it
+        from the checkpoint's step count.  The 16-byte record {mult, k} is allocated at the first enabling -- before a step is
+        captured, a captured step allocates nothing.  The descriptor travels by value in the kernel arguments, so it is among the
+        scalars a captured step bakes in: a replay after it changed raises.  lr_now() reads the record."""
+        if schedule is None:
+            self._lr_sched, self._lr_desc = None, None
+            return
+        desc = schedule.descriptor()
+        if not isinstance(desc, L.LrSchedule):
+            raise TypeError("set_lr_schedule: schedule.descriptor() must give a dpc_amd._lib.LrSchedule")
+        self._lr_alloc()
+        self._lr_sched, self._lr_desc = schedule, desc
+
+    def _lr_alloc(self):
+        if self._lr_state is None:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise L.DpcError("set_lr_schedule: enable the schedule before a step is captured (it allocates its device record)")
+            host = torch.frombuffer(bytearray(bytes(L.LrState(mult=1.0, k=-1))), dtype=torch.uint8)   # (no step taken yet)
+            self._lr_state = host.to(self.device)
+
+    @property
+    def lr_schedule(self):
+        """the schedule set_lr_schedule was given, or None while it is off"""
+        return self._lr_sched
+
+    def lr_now(self) -> dict:
+        """the multiplier the last scheduled step used: {'mult', 'k', 'lr'} with lr = float32(self.lr) * mult as the one-group update
+        forms it (with parameter groups: the base lr of each group times mult).  k = -1 before the first scheduled step.  One
+        16-byte device-to-host copy; the step itself never calls it."""
+        if self._lr_state is None:
+            raise RuntimeError("lr_now: the learning-rate schedule was never enabled (set_lr_schedule)")
+        st = L.LrState.from_buffer_copy(self._lr_state.cpu().numpy().tobytes())
+        lr = float(torch.tensor(self.lr, dtype=torch.float32) * torch.tensor(st.mult, dtype=torch.float32))
+        return {"mult": st.mult, "k": st.k, "lr": lr}
+
+    def _adam_step_sched(self, grad_scale: float):
+        """adam_step() with the schedule on: the eight arms (guard x EMA x groups) through dpc_step_advance_sched and the _sched
+        entries, which take the guard's record and the average as nullable arguments -- the launches of the unscheduled arms, one
+        for one"""
+        st = None
+        seg, nseg = (self._seg_dev, self._seg_n) if self._groups else (None, 0)
+        if self._guard is not None:
+            max_norm, skip_nonfinite = self._guard
+            st = self._guard_state
+            self.call("dpc_grad_sumsq", self.flat_g, self.numel, seg, nseg, self._guard_partials)
+            self.call("dpc_grad_verdict", self._guard_partials, L.GRAD_PARTIALS, max_norm or 0.0, int(skip_nonfinite), st)
+        self.call("dpc_step_advance_sched", self.dev_step, self.dev_bc, 0.9, 0.999, st, C.byref(self._lr_desc), self._lr_state)
+        ema, step, decay = (self.flat_ema, self.dev_step, self._ema) if self._ema is not None else (None, None, 0.0)
+        if self._groups:
+            self.call("dpc_adam_groups_dev_sched", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, seg, nseg,
+                      0.9, 0.999, 1e-8, self.dev_bc, grad_scale, st, ema, step, decay, self._lr_state)
+        else:
+            self.call("dpc_adam_dev_sched", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
+                      self.wd, self.dev_bc, grad_scale, st, ema, step, decay, self._lr_state)
+
     def _count_step(self):
         """one more attempted optimizer step on the host mirror; with skip_nonfinite the device may have counted none"""
         self._step_count += 1
@@ -1316,6 +1385,8 @@ class BackboneEngine:
     def adam_step(self, grad_scale: float = 1.0):
         self._not_swapped("adam_step")
         self._count_step()
+        if self._lr_desc is not None:
+            return self._adam_step_sched(grad_scale)
         if self._ema is not None:
             return self._adam_step_ema(grad_scale)
         if self._guard is not None:
@@ -1369,7 +1440,10 @@ class BackboneEngine:
         if self._guard is not None:
             base = base + (("grad_guard",) + self._guard,)
         # ... and with the parameter average its decay (again only then)
-        return base + (("ema", self._ema),) if self._ema is not None else base
+        if self._ema is not None:
+            base = base + (("ema", self._ema),)
+        # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
+        return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
     def check_graph_capture(self):
         """raises the DpcError every capture raises when this engine cannot capture a step (it does not run on the HIP device)"""
@@ -1439,7 +1513,7 @@ class BackboneEngine:
             if eng is None:
                 raise RuntimeError(f"replay of a captured {what} step whose engine is gone")
             if eng._baked_scalars() != baked:   # loud, not stale: the graph would go on stepping with the values of its capture
-                raise RuntimeError(f"lr / wd / dropout / gradient guard / EMA decay changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
+                raise RuntimeError(f"lr / wd / dropout / gradient guard / EMA decay / lr schedule changed since this step was captured ({baked} -> {eng._baked_scalars()}): "
                                    f"call {again}")
             return run(eng, graphs)
 

@@ -129,6 +129,64 @@ def open_ema(eng, args, rank: int = 0):
     return eng.ema_weights if args.ema_eval else contextlib.nullcontext
 
 
+def add_schedule_flags(parser):
+    """--lr_schedule and its parameters, of both entries (BackboneEngine.set_lr_schedule)"""
+    parser.add_argument('--lr_schedule', default='', choices=['', 'constant', 'cosine', 'linear', 'multistep'], help='scale the learning rate '
+                        'of every parameter group by a per-step multiplier evaluated on the device inside the fused optimizer step (no extra '
+                        'launch, no host work per step; works under --graph and --resident): after --warmup_steps of linear warm-up, constant, '
+                        'cosine or linear decay to --lr_min_mult at --total_steps, or --lr_gamma at each of --lr_milestones.  Counted in '
+                        'completed optimizer steps: a skipped step does not advance it, a resumed run continues it.  Default: off')
+    parser.add_argument('--warmup_steps', default=0, type=int, help='optimizer steps of linear warm-up, multiplier (k + 1) / N at step k; alone it '
+                        'means --lr_schedule constant')
+    parser.add_argument('--total_steps', default=0, type=int, help='where cosine / linear decay ends (default: epochs x steps per epoch of this rank; with --frames that is known only once '
+                        'a rank has opened its source, so pass the value to have it checked before the ranks start)')
+    parser.add_argument('--lr_min_mult', default=0.0, type=float, help='the multiplier cosine / linear decay ends at and keeps, in [0, 1]')
+    parser.add_argument('--lr_milestones', default='', type=str, help='multistep: comma-separated optimizer steps, strictly ascending, at most 8')
+    parser.add_argument('--lr_gamma', default=0.1, type=float, help='multistep: the factor per milestone, in (0, 1]')
+
+
+def schedule_from_flags(args, default_total: int = 0):
+    """the LRSchedule the flags describe, or None without them; raises ValueError on what the launcher would refuse.  While
+    --total_steps is left to its default and `default_total` is not known yet, the decay's end is not checked"""
+    from .optim import LRSchedule
+    kind = args.lr_schedule or ('constant' if args.warmup_steps else '')
+    if not kind:
+        stray = [f for f, given in (('--total_steps', args.total_steps != 0), ('--lr_min_mult', args.lr_min_mult != 0.0),
+                                    ('--lr_milestones', args.lr_milestones != ''), ('--lr_gamma', args.lr_gamma != 0.1)) if given]
+        if stray:
+            raise ValueError('{} set the parameters of --lr_schedule, which is missing'.format(' / '.join(stray)))
+        return None
+    try:
+        milestones = tuple(int(m) for m in args.lr_milestones.split(',') if m.strip() != '')
+    except ValueError:
+        raise ValueError('--lr_milestones must be comma-separated step counts, got {!r}'.format(args.lr_milestones))
+    if args.total_steps < 0:
+        raise ValueError('--total_steps must not be negative')
+    total = args.total_steps or default_total
+    if kind in ('cosine', 'linear') and not total:
+        total = max(args.warmup_steps, 0) + 1   # (placeholder: the other fields are checked now, the end when it is known)
+    return LRSchedule(kind, args.warmup_steps, total, args.lr_min_mult, milestones, args.lr_gamma)
+
+
+def check_schedule_flags(args, steps_per_epoch: int = 0):
+    """what the entries refuse before they start a rank.  steps_per_epoch: of synthetic input, where it is known here, so that the
+    default --total_steps is checked against --warmup_steps as well; 0 leaves that to open_schedule"""
+    schedule_from_flags(args, args.epochs * steps_per_epoch)
+
+
+def open_schedule(eng, args, steps_per_epoch: int, rank: int = 0):
+    """turns the schedule on from the flags (before any step is captured) and returns the tail of a printed train line, ' lr 1.000e-03'
+    of the step just taken (one 16-byte copy; every rank holds the same value) -- or None without the flags: the output then stays
+    byte for byte what it was"""
+    schedule = schedule_from_flags(args, args.epochs * steps_per_epoch)
+    if schedule is None:
+        return None
+    eng.set_lr_schedule(schedule)
+    if rank == 0:
+        print('LR schedule: {}'.format(schedule.describe()), flush=True)
+    return lambda: ' lr {:.3e}'.format(eng.lr_now()['lr'])
+
+
 class StepDriver:
     """The steps of a run, eager or replayed.  Without ``graph`` every step is eager.  With it, per RUN (not per epoch) the first two
     train steps and the first validation step are eager -- they size every lazy buffer --; from then on the engine is asked once

@@ -66,7 +66,8 @@ import time
 
 import torch
 
-from .entry import GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, check_ema_flags, launch, open_ema, open_rank, world_size
+from .entry import (GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+                    check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -137,6 +138,7 @@ def build_parser() -> argparse.ArgumentParser:
                         'windows, for a DPC checkpoint, which carries no running statistics (an embedding then depends on its chunk)')
     add_guard_flags(parser)
     add_ema_flags(parser)
+    add_schedule_flags(parser)
     return parser
 
 
@@ -301,6 +303,7 @@ def _worker(rank: int, world: int, args, port: int):
             eng.lr = lrs[-1]   # the log line's lr: the head group's
 
     set_lr(lr_multiplier(0, 0.1, milestones, 1))  # LambdaLR's constructor step
+    resumed = None
     for path, what in ((args.test, 'test'), (args.retrieval, 'test'), (args.resume, 'resume'), (args.pretrain, 'pretrain')):   # --retrieval loads like --test
         if not path or path == 'random' or (what == 'pretrain' and args.resume):
             continue
@@ -329,6 +332,8 @@ def _worker(rank: int, world: int, args, port: int):
             best_acc = float(ck.get('best_acc', 0.0))
             iteration = int(ck.get('iteration', 0))
             ckpt.load_ema_state(eng, ck, path)
+            if 'lr_schedule' in ck:   # compared once the run's own schedule is known (open_schedule below)
+                resumed = ({'lr_schedule': ck['lr_schedule']}, path)
             if not args.reset_lr and 'optimizer' in ck:
                 if groups is None:
                     ckpt.load_optimizer_state(eng, ck['optimizer'])  # restores the group's lr as optimizer.load_state_dict does
@@ -444,6 +449,11 @@ def _worker(rank: int, world: int, args, port: int):
             # a replay reads the labels as they stand: the feed's are set in front of it (synthetic ones are drawn inside the graph)
             return steps.step(train, eager, (lambda: eng.set_labels(y)) if y is not None else None)[0]
 
+        # The per-step schedule multiplies whatever the epoch schedule (set_lr) has put into eng.lr / the segment table: on before the
+        # first capture, and among the baked values, so the captures set_lr asks for after a milestone carry it too
+        lr_tail = open_schedule(eng, args, len(src_train) if src_train is not None else args.synthetic, rank)
+        if resumed is not None:
+            ckpt.check_lr_schedule(eng, *resumed)
         for epoch in range(args.start_epoch, args.epochs):
             n_train = len(src_train) if src_train is not None else args.synthetic
             feed = src_train.epoch(dev) if src_train is not None and not args.resident else None
@@ -454,7 +464,7 @@ def _worker(rank: int, world: int, args, port: int):
                 if idx % args.print_freq == 0:
                     loss, acc = reduce(res)
                     log('Epoch: [{0}][{1}/{2}]\t Loss {3:.4f}\t Acc: {4:.4f}\t lr {5:g}'.format(epoch, idx, n_train, loss, acc, eng.lr) +
-                        (guard.gnorm() if guard and rank == 0 else ''), flush=True)
+                        (guard.gnorm() if guard and rank == 0 else '') + (lr_tail() if lr_tail and rank == 0 else ''), flush=True)
                     iteration += 1  # advanced on logged steps only, as the reference does (eval/test.py:262-270)
             line = steps.replay_line(args.batch_size)
             if line:
@@ -483,6 +493,8 @@ def _worker(rank: int, world: int, args, port: int):
                          'best_acc': best_acc, 'iteration': iteration,
                          'optimizer': (ckpt.optimizer_state_dict(eng) if groups is None else
                                        ckpt.grouped_optimizer_state_dict(eng, [g for g in eng.param_groups if not g['frozen']]))}
+                if eng.lr_schedule is not None:
+                    state['lr_schedule'] = ckpt.lr_schedule_entry(eng)
                 if eng.ema_decay is not None:
                     state['ema'] = ckpt.ema_entry(eng, state['state_dict'])
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
@@ -500,6 +512,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
+    check_schedule_flags(args, 0 if args.frames else args.synthetic)
     world = world_size(args)
     if args.resident and not args.frames:
         raise ValueError('--resident holds the --frames array in HBM: --frames is missing')

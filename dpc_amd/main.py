@@ -29,7 +29,8 @@ import time
 
 import torch
 
-from .entry import GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, check_ema_flags, launch, open_ema, open_rank, world_size
+from .entry import (GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+                    check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -77,6 +78,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--val_offsets', default='', type=str, help='--offsets of the --val_frames array')
     add_guard_flags(parser)
     add_ema_flags(parser)
+    add_schedule_flags(parser)
     return parser
 
 
@@ -130,11 +132,14 @@ def _worker(rank: int, world: int, args, port: int):
     init = DPC_RNN(args.img_dim, args.num_seq, args.seq_len, args.pred_step, args.net, widths=widths, seed=0)  # same on every rank
     eng.load_params({k: v.detach() for k, v in init.named_parameters()})
     best_acc, iteration = 0.0, 0
+    resumed = None   # (the file's 'lr_schedule' entry, its path): compared once the run's own schedule is known (open_schedule below)
     ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
-            info = ckpt.resume(eng, args.resume, reset_lr=args.reset_lr)
+            info = ckpt.resume(eng, args.resume, reset_lr=args.reset_lr, check_schedule=False)
+            if 'lr_schedule' in info:
+                resumed = ({'lr_schedule': info['lr_schedule']}, args.resume)
             args.start_epoch, iteration, best_acc = info['epoch'], info['iteration'], info['best_acc']
             if args.reset_lr:
                 eng.lr, eng.wd = args.lr, args.wd
@@ -191,6 +196,9 @@ def _worker(rank: int, world: int, args, port: int):
     if args.resident:
         refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
     guard = GuardLog.open(eng, args)   # before the first capture: the guard's settings are baked into a captured step
+    lr_tail = open_schedule(eng, args, len(src_train) if src_train is not None else args.synthetic, rank)   # before the first capture, like the guard
+    if resumed is not None:
+        ckpt.check_lr_schedule(eng, *resumed)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def validate(block):   # validate(): dropout off, BN still batch statistics (dpc/main.py:249-282, model_3d.py:28)
@@ -222,7 +230,7 @@ def _worker(rank: int, world: int, args, port: int):
                     a.update(v, per_gpu)
                 if train and rank == 0:
                     print('Epoch: [{0}][{1}/{2}]\t Loss {3:.6f} ({4:.4f})\t Acc: top1 {5:.4f}; top3 {6:.4f}; top5 {7:.4f} T:{8:.2f}\t'.format(
-                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else ''), flush=True)
+                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else '') + (lr_tail() if lr_tail else ''), flush=True)
                 if train:
                     iteration += 1
         line = steps.replay_line(args.batch_size)
@@ -262,6 +270,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
+    check_schedule_flags(args, 0 if args.frames else args.synthetic)
     if args.resident and not args.frames:
         raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')
     if _simulator is not None and world_size(args) != 1:

@@ -33,8 +33,18 @@ arena: three launches whatever the number of parameters, the norm returned as a 
 Parameter average: ``Adam(..., ema_decay=0.999)`` keeps an exponential moving average of the parameters inside the same fused step
 (``BackboneEngine.set_ema``); ``with ema_weights(optimizer):`` shows the averaged values through ``model.parameters()`` for
 evaluation and puts the trained ones back on exit.
+
+Learning-rate schedule: ``Adam(..., lr_schedule=LRSchedule("cosine", warmup_steps=500, total_steps=20000))`` scales every group's
+``lr`` by a multiplier the device evaluates from its own step counter inside the fused step (``BackboneEngine.set_lr_schedule``):
+no host write per step, and it works in a replayed hipGraph.  The groups' ``lr`` stay the base values.  ``lr_multiplier(k,
+schedule)`` is the same function on the host, e.g. for ``LambdaLR(optimizer, lambda k: lr_multiplier(k, schedule))`` over a torch
+optimizer; ``LambdaLR`` over this optimizer keeps working as before (use one or the other).
 """
 from __future__ import annotations
+
+import dataclasses
+import math
+from typing import Optional, Tuple
 
 import torch
 
@@ -45,9 +55,94 @@ from . import checkpoint as ckpt
 from .engine import engine_of
 
 
+LR_KINDS = {"constant": L.LR_CONSTANT, "cosine": L.LR_COSINE, "linear": L.LR_LINEAR, "multistep": L.LR_MULTISTEP}
+
+
+@dataclasses.dataclass(frozen=True)
+class LRSchedule:
+    """A learning-rate multiplier as a function of k, the number of completed optimizer steps (see lr_multiplier).  Step counts, not
+    epochs; one multiplier for all parameter groups.  Checked where it is built, on the conditions the launcher refuses."""
+    kind: str = "constant"
+    warmup_steps: int = 0
+    total_steps: int = 0              # cosine, linear: where the decay ends
+    min_mult: float = 0.0             # cosine, linear: the multiplier from total_steps on
+    milestones: Tuple[int, ...] = ()  # multistep: optimizer steps, strictly ascending, at most 8
+    gamma: float = 0.1                # multistep
+
+    def __post_init__(self):
+        object.__setattr__(self, "milestones", tuple(int(m) for m in self.milestones))
+        for f in ("warmup_steps", "total_steps"):
+            object.__setattr__(self, f, int(getattr(self, f)))
+        for f in ("min_mult", "gamma"):
+            object.__setattr__(self, f, float(getattr(self, f)))
+        if self.kind not in LR_KINDS:
+            raise ValueError(f"LRSchedule: kind must be one of {sorted(LR_KINDS)}, got {self.kind!r}")
+        if not 0 <= self.warmup_steps < 2 ** 31:
+            raise ValueError(f"LRSchedule: warmup_steps must be a non-negative step count, got {self.warmup_steps}")
+        if self.kind in ("cosine", "linear"):
+            if not self.warmup_steps < self.total_steps < 2 ** 31:
+                raise ValueError(f"LRSchedule: {self.kind} needs total_steps > warmup_steps, got {self.total_steps} and {self.warmup_steps}")
+            if not 0.0 <= self.min_mult <= 1.0:
+                raise ValueError(f"LRSchedule: min_mult must lie in [0, 1], got {self.min_mult}")
+        if self.kind == "multistep":
+            ms = self.milestones
+            if len(ms) > L.LR_MAX_MILESTONES:
+                raise ValueError(f"LRSchedule: at most {L.LR_MAX_MILESTONES} milestones, got {len(ms)}")
+            if any(not 0 <= m < 2 ** 31 for m in ms) or any(b <= a for a, b in zip(ms, ms[1:])):
+                raise ValueError(f"LRSchedule: milestones must be non-negative and strictly ascending, got {ms}")
+            if not 0.0 < self.gamma <= 1.0:
+                raise ValueError(f"LRSchedule: gamma must lie in (0, 1], got {self.gamma}")
+
+    def descriptor(self) -> "L.LrSchedule":
+        """struct dpc_lr_schedule, with the fields the kind does not read left at zero"""
+        d = L.LrSchedule(kind=LR_KINDS[self.kind], warmup_steps=self.warmup_steps)
+        if self.kind in ("cosine", "linear"):
+            d.total_steps, d.min_mult = self.total_steps, self.min_mult
+        if self.kind == "multistep":
+            d.n_milestones, d.gamma = len(self.milestones), self.gamma
+            for i, m in enumerate(self.milestones):
+                d.milestones[i] = m
+        return d
+
+    def to_dict(self) -> dict:
+        """the fields the kind reads (the checkpoint's 'lr_schedule' entry)"""
+        out = {"kind": self.kind, "warmup_steps": self.warmup_steps}
+        if self.kind in ("cosine", "linear"):
+            out.update(total_steps=self.total_steps, min_mult=self.min_mult)
+        if self.kind == "multistep":
+            out.update(milestones=list(self.milestones), gamma=self.gamma)
+        return out
+
+    def describe(self) -> str:
+        d = self.to_dict()
+        return d.pop("kind") + "".join(f", {k} {v}" for k, v in d.items())
+
+
+def lr_multiplier(k: int, schedule: LRSchedule) -> float:
+    """The multiplier of the step taken after k completed optimizer steps -- what the device writes into its record, rounded to f32
+    there.  Python floats (doubles), one rounding per operation, in the kernel's order (csrc/loss.hip: lr_mult)."""
+    s, k = schedule, int(k)
+    W = s.warmup_steps
+    if k < W:
+        return (k + 1) / W
+    if s.kind in ("cosine", "linear"):
+        m0 = s.min_mult
+        x = (k - W) / (s.total_steps - W)
+        if x >= 1.0:
+            return m0
+        shape = 0.5 * (1.0 + math.cos(3.141592653589793 * x)) if s.kind == "cosine" else 1.0 - x
+        return m0 + (1.0 - m0) * shape
+    mult = 1.0
+    if s.kind == "multistep":
+        for m in s.milestones:
+            if m <= k:
+                mult *= s.gamma
+    return mult
+
+
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False,
-                 max_grad_norm=None, skip_nonfinite: bool = False, ema_decay=None):
+                 max_grad_norm=None, skip_nonfinite: bool = False, ema_decay=None, lr_schedule: Optional[LRSchedule] = None):
         if amsgrad:
             raise ValueError("amsgrad is not supported (the reference does not use it, dpc/main.py:80-81)")
         if tuple(betas) != (0.9, 0.999) or eps != 1e-8:
@@ -66,6 +161,9 @@ class Adam(torch.optim.Optimizer):
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be None or lie in (0, 1), got {ema_decay}")
         self._ema = ema_decay   # None: the engine's average is left as it is
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError(f"lr_schedule must be None or an LRSchedule, got {lr_schedule!r}")
+        self._lr_schedule = lr_schedule   # None: the engine's schedule is left as it is
         self._pending_state = None
         self._by_ptr = None     # (engine, {arena address: parameter name})
         self._updated = set()   # names of the parameters that have been updated at least once (torch creates their state then)
@@ -124,6 +222,8 @@ class Adam(torch.optim.Optimizer):
             eng.set_grad_guard(*self._guard)
         if self._ema is not None and eng.ema_decay != float(self._ema):
             eng.set_ema(self._ema)
+        if self._lr_schedule is not None and eng.lr_schedule != self._lr_schedule:
+            eng.set_lr_schedule(self._lr_schedule)
         eng.adam_step()
         self._updated.update(k for have in live for k in have)
         eng.packed_for_step = -1

@@ -390,6 +390,49 @@ int dpc_adam_groups_dev_ema(float* p, const float* g, float* m, float* v, int64_
                             int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
                             const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev, float decay, dpc_stream_t stream);
 int dpc_arena_swap(float* a, float* b, int64_t n, dpc_stream_t stream);
+/* ---- per-step learning-rate schedule inside the fused step (csrc/loss.hip).  k = completed optimizer steps before this one
+ * (step_dev[0] before the advance; the index LambdaLR passes its lambda).  Every group steps with lr_group * mult(k); mult in double,
+ * rounded to f32 once:
+ *     k < W                : (k + 1) / W                                          W = warmup_steps >= 0
+ *     else, x = min(1, (k - W) / (T - W)), T = total_steps, m0 = min_mult in [0, 1]:
+ *       DPC_LR_CONSTANT    : 1
+ *       DPC_LR_COSINE      : m0 + (1 - m0) * 0.5 * (1 + cos(pi x))    (x >= 1: m0)
+ *       DPC_LR_LINEAR      : m0 + (1 - m0) * (1 - x)                  (x >= 1: m0)
+ *       DPC_LR_MULTISTEP   : gamma ^ #{milestones <= k}   (steps, strictly ascending, non-negative, at most 8; 0 < gamma <= 1)
+ * cosine and linear need T > W.  The descriptor is host memory, validated by the launcher (DPC_ERR_ARG, nothing launched) and passed
+ * to the kernel by value: no device table, no upload.
+ *   step_advance_sched  dpc_step_advance (state_dev null) or dpc_step_advance_gated (state_dev given) -- step and bias_corr get the
+ *                same bits -- and lr_state_dev = {mult(k), k}, plain stores of one thread.  On state_dev->skip nothing is written.
+ *   adam_dev_sched / adam_groups_dev_sched   the _ema entries with the step size (lr * lr_state_dev->mult) / bias_corr1, the product
+ *                in f32 first; lr_state_dev non-null.  ema and step_dev may be null (both): no average, `decay` ignored. */
+#define DPC_LR_CONSTANT 0
+#define DPC_LR_COSINE 1
+#define DPC_LR_LINEAR 2
+#define DPC_LR_MULTISTEP 3
+#define DPC_LR_MAX_MILESTONES 8
+typedef struct dpc_lr_schedule {
+    int32_t kind;           /* DPC_LR_* */
+    int32_t warmup_steps;
+    int32_t total_steps;    /* cosine, linear */
+    int32_t n_milestones;   /* multistep */
+    double min_mult;        /* cosine, linear */
+    double gamma;           /* multistep */
+    int32_t milestones[DPC_LR_MAX_MILESTONES];
+} dpc_lr_schedule;          /* 64 bytes */
+typedef struct dpc_lr_state {
+    float mult;             /* mult(k) of the last step that was not skipped */
+    int32_t k;
+    int32_t reserved[2];
+} dpc_lr_state;             /* 16 bytes, device memory */
+int dpc_step_advance_sched(int32_t* step_dev, float* bias_corr_dev, double beta1, double beta2, const dpc_grad_state* state_dev,
+                           const dpc_lr_schedule* schedule, dpc_lr_state* lr_state_dev, dpc_stream_t stream);
+int dpc_adam_dev_sched(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+                       float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev, float* ema,
+                       const int32_t* step_dev, float decay, const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
+int dpc_adam_groups_dev_sched(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                              int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
+                              const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev, float decay,
+                              const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
 /* counter_dev[0] += 1 on the stream: the dropout draw counter (one draw per train-mode forward; the `step_dev` the recurrence and
  * the classifier head key their Philox masks on), graph-capturable like dpc_step_advance */
 int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream);
