@@ -73,6 +73,26 @@ class GradState(C.Structure):
 
 GRAD_PARTIALS = 1024   # DPC_GRAD_PARTIALS
 
+
+class LambSegment(C.Structure):
+    """struct dpc_lamb_segment (include/dpc_hip.h): one per parameter slot; chunk0 / n_chunks are filled by dpc_lamb_build_chunks"""
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("weight_decay", C.c_float), ("active", C.c_int32),
+                ("adapt", C.c_int32), ("chunk0", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class LambChunk(C.Structure):
+    """struct dpc_lamb_chunk (include/dpc_hip.h)"""
+    _fields_ = [("begin", C.c_int64), ("len", C.c_int32), ("seg", C.c_int32)]
+
+
+class LambRecord(C.Structure):
+    """struct dpc_lamb_record (include/dpc_hip.h): a segment's norms and trust ratio of the last LAMB step, in device memory"""
+    _fields_ = [("sum_p2", C.c_double), ("sum_u2", C.c_double), ("pnorm", C.c_float), ("unorm", C.c_float), ("ratio", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+LAMB_CHUNK = 4096   # DPC_LAMB_CHUNK
+
 LR_CONSTANT, LR_COSINE, LR_LINEAR, LR_MULTISTEP = 0, 1, 2, 3   # DPC_LR_* (include/dpc_hip.h)
 LR_MAX_MILESTONES = 8   # DPC_LR_MAX_MILESTONES
 
@@ -183,6 +203,12 @@ _SIGS = {
     "dpc_step_advance_sched": [_vp, _vp, _f64, _f64, _vp, C.POINTER(LrSchedule), _vp, _vp],
     "dpc_adam_dev_sched": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
     "dpc_adam_groups_dev_sched": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
+    "dpc_adamw_dev": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
+    "dpc_adamw_groups_dev": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _vp],
+    "dpc_lamb_build_chunks": [C.POINTER(LambSegment), _i32, _i64, C.POINTER(LambChunk), _i32],
+    "dpc_lamb_moments": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp],
+    "dpc_lamb_ratios": [_vp, _i32, _vp, _i32, _vp, _vp, _vp],
+    "dpc_lamb_apply": [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
     "dpc_counter_advance": [_vp, _vp],
     "dpc_copy2d_f32": [_vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "dpc_copy2d_multi": [_vp, _i32, _i32, _vp],

@@ -48,9 +48,11 @@ def model_state_dict(eng, prefix: str = "module.") -> "Dict[str, torch.Tensor]":
     return ordered
 
 
-def _adam_group_defaults(lr: float, wd: float) -> dict:
-    """hyper-parameter keys/values torch.optim.Adam(params, lr=lr, weight_decay=wd) of the installed torch writes"""
-    probe = torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))], lr=lr, weight_decay=wd)
+def _adam_group_defaults(lr: float, wd: float, kind: str = "adam") -> dict:
+    """hyper-parameter keys/values torch.optim.Adam(params, lr=lr, weight_decay=wd) of the installed torch writes -- under the
+    engine's "adamw" update rule torch.optim.AdamW's, so that the file continues there (LAMB, which torch does not have, keeps Adam's)"""
+    cls = torch.optim.AdamW if kind == "adamw" else torch.optim.Adam
+    probe = cls([torch.nn.Parameter(torch.zeros(1))], lr=lr, weight_decay=wd)
     g = dict(probe.state_dict()["param_groups"][0])
     g.pop("params")
     return g
@@ -66,7 +68,7 @@ def optimizer_state_dict(eng) -> dict:
             state[i] = {"step": torch.tensor(float(eng.step_count)),
                         "exp_avg": eng.flat_m[o:o + n].detach().cpu().clone().view(eng.shapes[k]),
                         "exp_avg_sq": eng.flat_v[o:o + n].detach().cpu().clone().view(eng.shapes[k])}
-    group = _adam_group_defaults(eng.lr, eng.wd)
+    group = _adam_group_defaults(eng.lr, eng.wd, eng.optimizer_kind)
     group["params"] = list(range(len(names)))
     return {"state": state, "param_groups": [group]}
 
@@ -86,7 +88,7 @@ def grouped_optimizer_state_dict(eng, groups, updated=None) -> dict:
                             "exp_avg": eng.flat_m[o:o + n].detach().cpu().clone().view(eng.shapes[k]),
                             "exp_avg_sq": eng.flat_v[o:o + n].detach().cpu().clone().view(eng.shapes[k])}
             i += 1
-        og = _adam_group_defaults(float(g["lr"]), float(g.get("weight_decay", 0.0)))
+        og = _adam_group_defaults(float(g["lr"]), float(g.get("weight_decay", 0.0)), eng.optimizer_kind)
         if "initial_lr" in g:
             og["initial_lr"] = g["initial_lr"]
         og["params"] = list(range(i - len(ks), i))
@@ -190,9 +192,17 @@ def check_lr_schedule(eng, ck: dict, path: str) -> None:
         warnings.warn(f"{path} was written under the learning-rate schedule {ck['lr_schedule']}, this run continues with {mine}")
 
 
+def check_optimizer_kind(eng, ck: dict, path: str) -> None:
+    """a resumed run takes its update rule from the flags or the caller, never from the file; one warning if the file was written
+    under another one.  A file without the entry (every Adam run's) says nothing."""
+    if "optimizer_kind" in ck and ck["optimizer_kind"] != eng.optimizer_kind:
+        warnings.warn(f"{path} was written under the optimizer {ck['optimizer_kind']}, this run continues with {eng.optimizer_kind}")
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
     """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
-    schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry)"""
+    schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
+    rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb")"""
     eng._not_swapped("build_state")
     state = {"epoch": epoch, "net": net, "state_dict": model_state_dict(eng), "best_acc": best_acc,
              "optimizer": optimizer_state_dict(eng), "iteration": iteration}
@@ -200,6 +210,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
         state["lr_schedule"] = lr_schedule_entry(eng)
     if eng.ema_decay is not None:
         state["ema"] = ema_entry(eng, state["state_dict"])
+    if eng.optimizer_kind != "adam":
+        state["optimizer_kind"] = eng.optimizer_kind
     return state
 
 
@@ -262,6 +274,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
         else:
             warnings.warn(f"{path} holds no optimizer state: Adam moments and step count start from zero")
     load_ema_state(eng, ck, path)
+    check_optimizer_kind(eng, ck, path)
     if check_schedule:
         check_lr_schedule(eng, ck, path)
     info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}

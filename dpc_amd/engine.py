@@ -541,6 +541,8 @@ class BackboneEngine:
         self._steps_unsure = False   # a step may have been skipped on the device since _step_count was last read from dev_step
         self._ema, self.flat_ema, self._ema_swapped = None, None, False   # parameter average of the fused Adam (set_ema, swap_ema)
         self._lr_sched, self._lr_desc, self._lr_state = None, None, None   # per-step learning-rate schedule of the fused Adam (set_lr_schedule)
+        self._opt_kind, self._opt_x1d, self._opt_key, self._opt_host = "adam", False, None, b""   # update rule of the fused step (set_optimizer)
+        self._lamb, self._aw_seg_dev, self._aw_seg_n = None, None, 0   # LAMB's device tables; AdamW's own segment table under exclude_1d
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -925,6 +927,10 @@ class BackboneEngine:
             self._lr_alloc()
             self._lr_state.copy_(old._lr_state)
             self._lr_sched, self._lr_desc = old._lr_sched, old._lr_desc
+        if old._opt_kind != "adam":   # the update rule, its tables and (LAMB) the records of its last step
+            self.set_optimizer(old._opt_kind, old._opt_x1d)
+            if old._lamb is not None and self._lamb is not None:
+                self._lamb["records"].copy_(old._lamb["records"])
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -1356,6 +1362,168 @@ class BackboneEngine:
             self.call("dpc_adam_dev_sched", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
                       self.wd, self.dev_bc, grad_scale, st, ema, step, decay, self._lr_state)
 
+    # ------------------------------------------------------------------ update rule of the fused step (csrc/optim_kinds.hip)
+    def set_optimizer(self, kind: str = "adam", exclude_1d: bool = False):
+        """Update rule of the fused step: "adam" (the default: torch.optim.Adam, weight decay folded into the gradient -- adam_step()
+        then runs exactly what it ran before this method existed), "adamw" (torch.optim.AdamW: the decay decoupled, one launch as
+        Adam) or "lamb" (You et al. 2020, bias-corrected: per parameter tensor the step is scaled by the trust ratio |p| / |u|; three
+        launches where Adam has one -- moments and per-chunk norms, per-tensor ratios, apply -- with nothing crossing the host, so it
+        works in a replayed step and every rank reaches the same bits without a collective).  The step counter, the gradient guard,
+        the parameter average and the learning-rate schedule work under all three.
+
+        exclude_1d (adamw / lamb only): no weight decay on parameters with at most one dimension (biases, BatchNorm), and under lamb
+        no trust ratio either (r = 1).  Learning rate, weight decay and frozen parameters come from the parameter groups when there
+        are groups, else from ``self.lr`` / ``self.wd``; the tables are rebuilt, and uploaded, when one of those changes -- here or at
+        the next adam_step(), never while a graph is being captured (that raises).  The device buffers are allocated once and keep
+        their addresses.  Kind, flag and table contents are among the values a captured step bakes in, while the kind is not adam.
+        lamb_stats() reads the last step's norms and ratios."""
+        if kind not in ("adam", "adamw", "lamb"):
+            raise ValueError(f"set_optimizer: kind must be 'adam', 'adamw' or 'lamb', got {kind!r}")
+        if exclude_1d and kind == "adam":
+            raise ValueError("set_optimizer: exclude_1d needs kind 'adamw' or 'lamb'")
+        if (kind, bool(exclude_1d)) == (self._opt_kind, self._opt_x1d):   # (a caller that passes its settings at every step)
+            if kind != "adam":
+                self._opt_sync()
+            return
+        self._opt_kind, self._opt_x1d, self._opt_key, self._opt_host = kind, bool(exclude_1d), None, b""
+        if kind != "adam":
+            self._opt_sync()
+
+    @property
+    def optimizer_kind(self) -> str:
+        return self._opt_kind
+
+    @property
+    def optimizer_exclude_1d(self) -> bool:
+        return self._opt_x1d
+
+    def _per_param_hyper(self):
+        """[(name, begin, end, lr, weight_decay, active)] in arena order: what the update does with every parameter slot"""
+        per = None
+        if self._groups:
+            per = {k: (g["lr"], g["weight_decay"], not g["frozen"]) for g in self._groups for k in g["params"]}
+        rows = []
+        for k, (o, n) in self.offsets.items():
+            lr, wd, active = per.get(k, (0.0, 0.0, False)) if per is not None else (float(self.lr), float(self.wd), True)
+            if not active:
+                lr = wd = 0.0
+            if self._opt_x1d and len(self.shapes[k]) <= 1:
+                wd = 0.0
+            rows.append((k, o, o + (n + 3) // 4 * 4, lr, wd, active))
+        return rows
+
+    def _opt_upload(self, dst: torch.Tensor, host: bytes):
+        raw = torch.frombuffer(bytearray(host), dtype=torch.uint8)
+        dst[:raw.numel()].copy_(raw)
+
+    def _opt_sync(self):
+        """(re)build the tables of the adamw / lamb step when what they are made from changed; upload what differs"""
+        key = (self._opt_kind, self._opt_x1d, float(self.lr), float(self.wd), self._groups_key)
+        if key == self._opt_key:
+            return
+        capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if self._opt_kind == "adamw" and not self._opt_x1d:   # the one-group update or the groups' own table: nothing of its own
+            self._opt_key, self._opt_host = key, b""
+            return
+        rows = self._per_param_hyper()
+        if self._opt_kind == "adamw":
+            segs = []
+            for _, b, e, lr, wd, active in rows:
+                if segs and segs[-1][1] == b and tuple(segs[-1][2:]) == (lr, wd, active):
+                    segs[-1][1] = e
+                else:
+                    segs.append([b, e, lr, wd, active])
+            if len(segs) > L.ADAM_MAX_SEGMENTS:
+                raise ValueError(f"set_optimizer: {len(segs)} segments, the kernel's table holds {L.ADAM_MAX_SEGMENTS}")
+            tab = (L.AdamSegment * len(segs))()
+            for i, (b, e, lr, wd, active) in enumerate(segs):
+                tab[i] = L.AdamSegment(b, e, lr, wd, int(active), 0)
+            host = bytes(tab)
+            if host != self._opt_host:
+                if capturing:
+                    raise L.DpcError("set_optimizer: the optimizer's table changed while a graph is being captured")
+                if self._aw_seg_dev is None:
+                    self._aw_seg_dev = torch.zeros(L.ADAM_MAX_SEGMENTS * C.sizeof(L.AdamSegment), dtype=torch.uint8, device=self.device)
+                self._opt_upload(self._aw_seg_dev, host)
+                self._aw_seg_n = len(segs)
+            self._opt_key, self._opt_host = key, host
+            return
+        # lamb: one table entry per parameter slot, and the chunk table that is the work split of its launches
+        if len(rows) > L.ADAM_MAX_SEGMENTS:
+            raise ValueError(f"set_optimizer: {len(rows)} parameters, the kernel's table holds {L.ADAM_MAX_SEGMENTS}")
+        cap = self.numel // L.LAMB_CHUNK + len(rows) + 1
+        tab = (L.LambSegment * len(rows))()
+        for i, (k, b, e, lr, wd, active) in enumerate(rows):
+            adapt = int(active and not (self._opt_x1d and len(self.shapes[k]) <= 1))
+            tab[i] = L.LambSegment(b, e, lr, wd, int(active), adapt, 0, 0)
+        chunks = (L.LambChunk * cap)()
+        nc = self.lib.call("dpc_lamb_build_chunks", tab, len(rows), self.numel, chunks, cap)
+        if nc <= 0:
+            raise ValueError("set_optimizer: no parameter is trained (every parameter is frozen)")
+        seg_host, chunk_host = bytes(tab), bytes(chunks)[:nc * C.sizeof(L.LambChunk)]
+        host = seg_host + chunk_host
+        if host != self._opt_host:
+            if capturing:
+                raise L.DpcError("set_optimizer: the optimizer's tables changed while a graph is being captured")
+            if self._lamb is None:   # allocated once, for the engine's life: a captured step holds these addresses
+                u8 = dict(dtype=torch.uint8, device=self.device)
+                self._lamb = {"seg": torch.zeros(L.ADAM_MAX_SEGMENTS * C.sizeof(L.LambSegment), **u8),
+                              "chunks": torch.zeros(cap * C.sizeof(L.LambChunk), **u8),
+                              "partials": torch.zeros(2 * cap, dtype=torch.float64, device=self.device),
+                              "records": torch.zeros(L.ADAM_MAX_SEGMENTS * C.sizeof(L.LambRecord), **u8)}
+            self._opt_upload(self._lamb["seg"], seg_host)
+            self._opt_upload(self._lamb["chunks"], chunk_host)
+        self._lamb.update(n_seg=len(rows), n_chunks=nc, names=[r[0] for r in rows],
+                          active=[bool(r[5]) for r in rows], adapt=[bool(t.adapt) for t in tab])
+        self._opt_key, self._opt_host = key, host
+
+    def lamb_stats(self, adaptive_only: bool = False) -> Dict[str, Tuple[float, float, float]]:
+        """{parameter name: (|p|, |u|, trust ratio)} of the last LAMB step over the trained parameters (adaptive_only: those that step
+        with a trust ratio).  One device-to-host copy; the step itself never calls it."""
+        if self._lamb is None:
+            raise RuntimeError("lamb_stats: LAMB was never enabled (set_optimizer('lamb'))")
+        lm = self._lamb
+        recs = (L.LambRecord * lm["n_seg"]).from_buffer_copy(lm["records"][:lm["n_seg"] * C.sizeof(L.LambRecord)].cpu().numpy().tobytes())
+        return {k: (r.pnorm, r.unorm, r.ratio) for k, r, a, ad in zip(lm["names"], recs, lm["active"], lm["adapt"])
+                if a and (ad or not adaptive_only)}
+
+    def _opt_step(self, grad_scale: float):
+        """adam_step() under adamw / lamb: the guard and the step advance as in the Adam arms, then the kind's own update.  The
+        entries take the guard's record, the average and the schedule's record as nullable arguments, so one path serves every arm."""
+        self._opt_sync()
+        st = None
+        seg, nseg = (self._seg_dev, self._seg_n) if self._groups else (None, 0)
+        if self._guard is not None:
+            max_norm, skip_nonfinite = self._guard
+            st = self._guard_state
+            self.call("dpc_grad_sumsq", self.flat_g, self.numel, seg, nseg, self._guard_partials)
+            self.call("dpc_grad_verdict", self._guard_partials, L.GRAD_PARTIALS, max_norm or 0.0, int(skip_nonfinite), st)
+        lrs = None
+        if self._lr_desc is not None:
+            lrs = self._lr_state
+            self.call("dpc_step_advance_sched", self.dev_step, self.dev_bc, 0.9, 0.999, st, C.byref(self._lr_desc), lrs)
+        elif st is not None:
+            self.call("dpc_step_advance_gated", self.dev_step, self.dev_bc, 0.9, 0.999, st)
+        else:
+            self.call("dpc_step_advance", self.dev_step, self.dev_bc, 0.9, 0.999)
+        ema, step, decay = (self.flat_ema, self.dev_step, self._ema) if self._ema is not None else (None, None, 0.0)
+        if self._opt_kind == "adamw":
+            if self._opt_x1d:
+                seg, nseg = self._aw_seg_dev, self._aw_seg_n
+            if seg is not None:
+                self.call("dpc_adamw_groups_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, seg, nseg,
+                          0.9, 0.999, 1e-8, self.dev_bc, grad_scale, st, ema, step, decay, lrs)
+            else:
+                self.call("dpc_adamw_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
+                          self.wd, self.dev_bc, grad_scale, st, ema, step, decay, lrs)
+            return
+        lm = self._lamb
+        self.call("dpc_lamb_moments", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, lm["seg"], lm["n_seg"], lm["chunks"],
+                  lm["n_chunks"], 0.9, 0.999, 1e-8, self.dev_bc, grad_scale, st, lm["partials"])
+        self.call("dpc_lamb_ratios", lm["seg"], lm["n_seg"], lm["partials"], lm["n_chunks"], st, lm["records"])
+        self.call("dpc_lamb_apply", self.flat_p, self.flat_m, self.flat_v, self.numel, lm["seg"], lm["n_seg"], lm["chunks"], lm["n_chunks"],
+                  1e-8, self.dev_bc, st, lm["records"], ema, step, decay, lrs)
+
     def _count_step(self):
         """one more attempted optimizer step on the host mirror; with skip_nonfinite the device may have counted none"""
         self._step_count += 1
@@ -1385,6 +1553,8 @@ class BackboneEngine:
     def adam_step(self, grad_scale: float = 1.0):
         self._not_swapped("adam_step")
         self._count_step()
+        if self._opt_kind != "adam":
+            return self._opt_step(grad_scale)
         if self._lr_desc is not None:
             return self._adam_step_sched(grad_scale)
         if self._ema is not None:
@@ -1442,6 +1612,9 @@ class BackboneEngine:
         # ... and with the parameter average its decay (again only then)
         if self._ema is not None:
             base = base + (("ema", self._ema),)
+        # ... and with another update rule than Adam its kind, its flag and its tables (only then)
+        if self._opt_kind != "adam":
+            base = base + (("optimizer", self._opt_kind, self._opt_x1d, self._opt_host),)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 

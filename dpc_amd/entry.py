@@ -187,6 +187,49 @@ def open_schedule(eng, args, steps_per_epoch: int, rank: int = 0):
     return lambda: ' lr {:.3e}'.format(eng.lr_now()['lr'])
 
 
+def add_optimizer_flags(parser):
+    """--optimizer / --wd_exclude_1d of both entries (BackboneEngine.set_optimizer)"""
+    parser.add_argument('--optimizer', default='adam', choices=['adam', 'adamw', 'lamb'], help='update rule of the fused optimizer step: adam '
+                        '(torch.optim.Adam, --wd folded into the gradient: the reference\'s), adamw (torch.optim.AdamW: --wd decoupled) or lamb '
+                        '(layer-wise trust ratio |p| / |u| per parameter tensor, for large batches).  All three run inside the step, on the '
+                        'device, under --graph, --resident, the gradient guard, --ema and --lr_schedule')
+    parser.add_argument('--wd_exclude_1d', action='store_true', help='no weight decay on parameters with at most one dimension (biases, '
+                        'BatchNorm); under lamb no trust ratio for them either.  Needs --optimizer adamw or lamb')
+
+
+def check_optimizer_flags(args):
+    """what the entries refuse before they start a rank"""
+    if args.wd_exclude_1d and args.optimizer == 'adam':
+        raise ValueError('--wd_exclude_1d needs --optimizer adamw or --optimizer lamb')
+
+
+class LambLog:
+    """What the entries print about the update rule.  ``open`` sets it from the flags (before any step is captured) and returns None
+    unless the rule is lamb; without the flags nothing is printed -- the output then stays byte for byte what it was."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    @classmethod
+    def open(cls, eng, args, rank: int = 0):
+        check_optimizer_flags(args)
+        if args.optimizer == 'adam':
+            return None
+        eng.set_optimizer(args.optimizer, args.wd_exclude_1d)
+        if rank == 0:
+            print('Optimizer: {}{}'.format(args.optimizer, ', wd_exclude_1d' if args.wd_exclude_1d else ''), flush=True)
+        return cls(eng) if args.optimizer == 'lamb' else None
+
+    def epoch_line(self) -> str:
+        """one read-back per epoch: the trust ratios of the epoch's last step over the adaptive, trained parameters"""
+        r = sorted(v[2] for v in self.eng.lamb_stats(adaptive_only=True).values())
+        if not r:
+            return 'LAMB: no adaptive parameter'
+        mid = len(r) // 2
+        median = r[mid] if len(r) % 2 else 0.5 * (r[mid - 1] + r[mid])
+        return 'LAMB: trust ratio min {:.3g} median {:.3g} max {:.3g}'.format(r[0], median, r[-1])
+
+
 class StepDriver:
     """The steps of a run, eager or replayed.  Without ``graph`` every step is eager.  With it, per RUN (not per epoch) the first two
     train steps and the first validation step are eager -- they size every lazy buffer --; from then on the engine is asked once

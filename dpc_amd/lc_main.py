@@ -66,7 +66,7 @@ import time
 
 import torch
 
-from .entry import (GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+from .entry import (GuardLog, LambLog, StepDriver, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
                     check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
@@ -139,6 +139,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_guard_flags(parser)
     add_ema_flags(parser)
     add_schedule_flags(parser)
+    add_optimizer_flags(parser)
     return parser
 
 
@@ -291,6 +292,8 @@ def _worker(rank: int, world: int, args, port: int):
     guard = GuardLog.open(eng, args)
     # the parameter average likewise, and before the loads below: each load re-seeds it, --resume then reads the file's own
     ema_eval = open_ema(eng, args, rank)
+    # the update rule likewise (--optimizer): its kind and tables are baked values too, and --resume compares the file's rule with it
+    lamb = LambLog.open(eng, args, rank)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def set_lr(mult, saved=None):
@@ -301,6 +304,8 @@ def _worker(rank: int, world: int, args, port: int):
             lrs = saved if saved is not None else [lr * mult for _, lr in groups]
             eng.set_param_groups([{'params': ks, 'lr': lr, 'weight_decay': args.wd} for (ks, _), lr in zip(groups, lrs)])
             eng.lr = lrs[-1]   # the log line's lr: the head group's
+        if args.optimizer != 'adam':   # the rule's own tables follow the new values here, eagerly: the next capture finds them uploaded
+            eng.set_optimizer(args.optimizer, args.wd_exclude_1d)
 
     set_lr(lr_multiplier(0, 0.1, milestones, 1))  # LambdaLR's constructor step
     resumed = None
@@ -332,6 +337,7 @@ def _worker(rank: int, world: int, args, port: int):
             best_acc = float(ck.get('best_acc', 0.0))
             iteration = int(ck.get('iteration', 0))
             ckpt.load_ema_state(eng, ck, path)
+            ckpt.check_optimizer_kind(eng, ck, path)
             if 'lr_schedule' in ck:   # compared once the run's own schedule is known (open_schedule below)
                 resumed = ({'lr_schedule': ck['lr_schedule']}, path)
             if not args.reset_lr and 'optimizer' in ck:
@@ -471,6 +477,8 @@ def _worker(rank: int, world: int, args, port: int):
                 log(line, flush=True)
             if guard and rank == 0:
                 log(guard.epoch_line(n_train), flush=True)
+            if lamb and rank == 0:
+                log(lamb.epoch_line(), flush=True)
             vl = va = 0.0
             n_val = len(src_val) if src_val is not None else max(args.synthetic // 4, 1)
             feed = src_val.epoch(dev) if src_val is not None and not args.resident else None
@@ -497,6 +505,8 @@ def _worker(rank: int, world: int, args, port: int):
                     state['lr_schedule'] = ckpt.lr_schedule_entry(eng)
                 if eng.ema_decay is not None:
                     state['ema'] = ckpt.ema_entry(eng, state['state_dict'])
+                if eng.optimizer_kind != 'adam':
+                    state['optimizer_kind'] = eng.optimizer_kind
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
         log('Training from ep %d to ep %d finished' % (args.start_epoch, args.epochs))
         if probe:
@@ -513,6 +523,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic)
+    check_optimizer_flags(args)
     world = world_size(args)
     if args.resident and not args.frames:
         raise ValueError('--resident holds the --frames array in HBM: --frames is missing')

@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from .entry import (GuardLog, StepDriver, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+from .entry import (GuardLog, LambLog, StepDriver, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
                     check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
@@ -79,6 +79,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_guard_flags(parser)
     add_ema_flags(parser)
     add_schedule_flags(parser)
+    add_optimizer_flags(parser)
     return parser
 
 
@@ -134,6 +135,7 @@ def _worker(rank: int, world: int, args, port: int):
     best_acc, iteration = 0.0, 0
     resumed = None   # (the file's 'lr_schedule' entry, its path): compared once the run's own schedule is known (open_schedule below)
     ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
+    lamb = LambLog.open(eng, args, rank)   # --optimizer: before --resume compares the file's rule with the run's, and before any capture
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -238,6 +240,8 @@ def _worker(rank: int, world: int, args, port: int):
             print(line, flush=True)
         if train and guard and rank == 0:
             print(guard.epoch_line(n_batches), flush=True)
+        if train and lamb and rank == 0:
+            print(lamb.epoch_line(), flush=True)
         return losses.local_avg, accs[0].local_avg, [a.local_avg for a in accs]
 
     for epoch in range(args.start_epoch, args.epochs):
@@ -271,6 +275,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic)
+    check_optimizer_flags(args)
     if args.resident and not args.frames:
         raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')
     if _simulator is not None and world_size(args) != 1:

@@ -141,6 +141,8 @@ def lr_multiplier(k: int, schedule: LRSchedule) -> float:
 
 
 class Adam(torch.optim.Optimizer):
+    _kind, _exclude_1d = "adam", False   # the engine's update rule (BackboneEngine.set_optimizer); AdamW and LAMB below change it
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, amsgrad: bool = False,
                  max_grad_norm=None, skip_nonfinite: bool = False, ema_decay=None, lr_schedule: Optional[LRSchedule] = None):
         if amsgrad:
@@ -224,6 +226,8 @@ class Adam(torch.optim.Optimizer):
             eng.set_ema(self._ema)
         if self._lr_schedule is not None and eng.lr_schedule != self._lr_schedule:
             eng.set_lr_schedule(self._lr_schedule)
+        if (eng.optimizer_kind, eng.optimizer_exclude_1d) != (self._kind, self._exclude_1d):
+            eng.set_optimizer(self._kind, self._exclude_1d)
         eng.adam_step()
         self._updated.update(k for have in live for k in have)
         eng.packed_for_step = -1
@@ -263,6 +267,27 @@ class Adam(torch.optim.Optimizer):
             self._pending_state = state_dict   # the engine does not exist yet: applied at the first step
             return
         self._load_into(eng, names, state_dict)
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW`` on the engine's fused step: the weight decay decoupled from the gradient (dpc_adamw_dev /
+    dpc_adamw_groups_dev, one launch as Adam).  Same keyword arguments as Adam; weight_decay defaults to torch's 1e-2."""
+    _kind = "adamw"
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+
+
+class LAMB(Adam):
+    """LAMB (You et al. 2020, bias-corrected) on the engine's fused step: per parameter tensor the step lr * u is scaled by the trust
+    ratio |p| / |u| (dpc_lamb_moments / dpc_lamb_ratios / dpc_lamb_apply).  exclude_1d: parameters with at most one dimension (biases,
+    BatchNorm) get no weight decay and no trust ratio.  Same keyword arguments as Adam otherwise."""
+    _kind = "lamb"
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 exclude_1d: bool = False, **kw):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
+        self._exclude_1d = bool(exclude_1d)
 
 
 def ema_weights(optimizer: Adam):

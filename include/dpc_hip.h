@@ -433,6 +433,64 @@ int dpc_adam_groups_dev_sched(float* p, const float* g, float* m, float* v, int6
                               int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
                               const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev, float decay,
                               const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
+/* ---- the other update rules of the fused step (csrc/optim_kinds.hip).  Betas, eps, bias_corr_dev, grad_scale, state_dev (the
+ * guard's record, nullable), ema / step_dev / decay (the average, nullable as a pair) and lr_state_dev (the schedule's record,
+ * nullable: multiplier 1) mean what they mean for the _sched entries; lr_eff = lr * lr_state_dev->mult, the f32 product first.
+ * With gg = g * grad_scale * coef,  m <- b1 m + (1 - b1) gg,  v <- b2 v + (1 - b2) gg^2  (no wd * p in the gradient):
+ *   adamw_dev / adamw_groups_dev   torch.optim.AdamW:  p <- p (1 - lr_eff wd), a product rounded on its own as param.mul_ does, then
+ *                p <- p - (lr_eff / bc1) m / (sqrt(v) / sqrt(bc2) + eps) as Adam; with wd = 0 p, m, v (and ema) get the bits of the
+ *                Adam entries.  One launch, as Adam; all four arenas 16-byte aligned.
+ *   LAMB (You et al. 2020, bias-corrected), three launches:  u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps) + wd p;  per segment
+ *                r = |p| / |u| when the segment is adaptive and both norms are > 0, else 1;  p <- p - lr_eff r u.
+ *     lamb_build_chunks (host)  validates a host segment table (sorted, non-overlapping, multiples of 4 inside [0, n), lr, wd >= 0),
+ *                cuts every ACTIVE segment into chunks of at most DPC_LAMB_CHUNK floats that never cross a segment, in table order,
+ *                and fills each segment's chunk0 / n_chunks.  Returns the number of chunks.  The work split of the launches below is
+ *                this table and nothing else.
+ *     lamb_moments  writes m, v in place over the chunks, forms u and writes partials[2c] = sum p^2, partials[2c + 1] = sum u^2 of
+ *                chunk c in f64 (every element widened before it is squared); p is only read.
+ *     lamb_ratios   one dpc_lamb_record per segment: the segment's pairs added in chunk order in f64, the norms, and the ratio
+ *                formed in f64 and rounded once.  An inactive segment: sums 0, ratio 1.  adapt = 0: ratio 1, norms still reported.
+ *     lamb_apply    recomputes u from the new m, v and the old p (the same device function: the same bits) and does p -= lr_eff r u,
+ *                then the average's lerp by the thread that wrote p.
+ *   No atomics, one writer per value, every combine in a fixed order.  On state_dev->skip none of the three loads or stores
+ *   anything, the records included.  Floats outside every chunk (gaps, inactive segments) are never loaded or stored in any arena. */
+#define DPC_LAMB_CHUNK 4096
+typedef struct dpc_lamb_segment {
+    int64_t begin, end;       /* floats, multiples of 4 */
+    float lr, weight_decay;
+    int32_t active;           /* 0 = frozen */
+    int32_t adapt;            /* 0 = no trust ratio (r = 1) */
+    int32_t chunk0, n_chunks; /* filled by dpc_lamb_build_chunks */
+    int32_t reserved[2];
+} dpc_lamb_segment;           /* 48 bytes */
+typedef struct dpc_lamb_chunk {
+    int64_t begin;            /* floats */
+    int32_t len;              /* floats, a multiple of 4, <= DPC_LAMB_CHUNK */
+    int32_t seg;
+} dpc_lamb_chunk;             /* 16 bytes */
+typedef struct dpc_lamb_record {
+    double sum_p2, sum_u2;
+    float pnorm, unorm, ratio;
+    int32_t reserved;
+} dpc_lamb_record;            /* 32 bytes */
+int dpc_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, double beta1, double beta2, float eps,
+                  float wd, const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev, float* ema,
+                  const int32_t* step_dev, float decay, const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
+int dpc_adamw_groups_dev(float* p, const float* g, float* m, float* v, int64_t n, const dpc_adam_segment* segments_dev,
+                         int32_t n_segments, double beta1, double beta2, float eps, const float* bias_corr_dev, float grad_scale,
+                         const dpc_grad_state* state_dev, float* ema, const int32_t* step_dev, float decay,
+                         const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
+int dpc_lamb_build_chunks(dpc_lamb_segment* segments, int32_t n_segments, int64_t n, dpc_lamb_chunk* chunks, int32_t capacity);
+int dpc_lamb_moments(const float* p, const float* g, float* m, float* v, int64_t n, const dpc_lamb_segment* segments_dev,
+                     int32_t n_segments, const dpc_lamb_chunk* chunks_dev, int32_t n_chunks, double beta1, double beta2, float eps,
+                     const float* bias_corr_dev, float grad_scale, const dpc_grad_state* state_dev, double* partials,
+                     dpc_stream_t stream);
+int dpc_lamb_ratios(const dpc_lamb_segment* segments_dev, int32_t n_segments, const double* partials, int32_t n_chunks,
+                    const dpc_grad_state* state_dev, dpc_lamb_record* records_dev, dpc_stream_t stream);
+int dpc_lamb_apply(float* p, const float* m, const float* v, int64_t n, const dpc_lamb_segment* segments_dev, int32_t n_segments,
+                   const dpc_lamb_chunk* chunks_dev, int32_t n_chunks, float eps, const float* bias_corr_dev,
+                   const dpc_grad_state* state_dev, const dpc_lamb_record* records_dev, float* ema, const int32_t* step_dev,
+                   float decay, const dpc_lr_state* lr_state_dev, dpc_stream_t stream);
 /* counter_dev[0] += 1 on the stream: the dropout draw counter (one draw per train-mode forward; the `step_dev` the recurrence and
  * the classifier head key their Philox masks on), graph-capturable like dpc_step_advance */
 int dpc_counter_advance(int32_t* counter_dev, dpc_stream_t stream);
