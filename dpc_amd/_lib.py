@@ -72,6 +72,7 @@ class GradState(C.Structure):
 
 
 GRAD_PARTIALS = 1024   # DPC_GRAD_PARTIALS
+ACCUM_ADD, ACCUM_FINISH = 0, 1   # DPC_ACCUM_* (include/dpc_hip.h): modes of dpc_grad_accumulate
 
 
 class LambSegment(C.Structure):
@@ -197,6 +198,7 @@ _SIGS = {
     "dpc_adam_dev_ex": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp],
     "dpc_adam_groups_dev_ex": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp],
     "dpc_grad_scale": [_vp, _i64, _vp, _i32, _vp, _vp],
+    "dpc_grad_accumulate": [_vp, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _f32, _vp],
     "dpc_adam_dev_ema": [_vp, _vp, _vp, _vp, _i64, _f32, _f64, _f64, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
     "dpc_adam_groups_dev_ema": [_vp, _vp, _vp, _vp, _i64, _vp, _i32, _f64, _f64, _f32, _vp, _f32, _vp, _vp, _vp, _f32, _vp],
     "dpc_arena_swap": [_vp, _vp, _i64, _vp],

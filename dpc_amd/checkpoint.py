@@ -199,11 +199,21 @@ def check_optimizer_kind(eng, ck: dict, path: str) -> None:
         warnings.warn(f"{path} was written under the optimizer {ck['optimizer_kind']}, this run continues with {eng.optimizer_kind}")
 
 
+def check_accum_steps(eng, ck: dict, path: str) -> None:
+    """a resumed run takes its accumulation from the flags or the caller, never from the file; one warning if the file was written
+    under another count.  A file without the entry (every run's without accumulation) counts as 1."""
+    if int(ck.get("accum_steps", 1)) != eng.accum_steps:
+        warnings.warn(f"{path} was written with {int(ck.get('accum_steps', 1))} micro-batches per optimizer step, this run continues "
+                      f"with {eng.accum_steps}")
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
     """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
     schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
-    rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb")"""
+    rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'.  Refused while an
+    accumulation cycle is open: the sum so far is not part of the file"""
     eng._not_swapped("build_state")
+    eng._not_mid_cycle("build_state")
     state = {"epoch": epoch, "net": net, "state_dict": model_state_dict(eng), "best_acc": best_acc,
              "optimizer": optimizer_state_dict(eng), "iteration": iteration}
     if eng.lr_schedule is not None:
@@ -212,6 +222,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
         state["ema"] = ema_entry(eng, state["state_dict"])
     if eng.optimizer_kind != "adam":
         state["optimizer_kind"] = eng.optimizer_kind
+    if eng.accum_steps > 1:
+        state["accum_steps"] = eng.accum_steps
     return state
 
 
@@ -275,6 +287,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
             warnings.warn(f"{path} holds no optimizer state: Adam moments and step count start from zero")
     load_ema_state(eng, ck, path)
     check_optimizer_kind(eng, ck, path)
+    check_accum_steps(eng, ck, path)
     if check_schedule:
         check_lr_schedule(eng, ck, path)
     info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}

@@ -543,6 +543,7 @@ class BackboneEngine:
         self._lr_sched, self._lr_desc, self._lr_state = None, None, None   # per-step learning-rate schedule of the fused Adam (set_lr_schedule)
         self._opt_kind, self._opt_x1d, self._opt_key, self._opt_host = "adam", False, None, b""   # update rule of the fused step (set_optimizer)
         self._lamb, self._aw_seg_dev, self._aw_seg_n = None, None, 0   # LAMB's device tables; AdamW's own segment table under exclude_1d
+        self._accum_n, self._accum_pos, self.flat_acc = 1, 0, None   # gradient accumulation in front of the fused step (set_grad_accum)
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -931,10 +932,15 @@ class BackboneEngine:
             self.set_optimizer(old._opt_kind, old._opt_x1d)
             if old._lamb is not None and self._lamb is not None:
                 self._lamb["records"].copy_(old._lamb["records"])
+        if old.flat_acc is not None:   # the accumulation: its setting, the sum so far and the position in the cycle
+            self._accum_alloc()
+            self.flat_acc.copy_(old.flat_acc)
+            self._accum_n, self._accum_pos = old._accum_n, old._accum_pos
         self.packed_for_step = -1
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         self._not_swapped("state_dict")
+        self._not_mid_cycle("state_dict")
         sd = {k: v.detach().clone() for k, v in self.PRM.items()}
         for k in list(sd):
             if k.startswith("agg.ConvGRUCell_00."):
@@ -1102,7 +1108,9 @@ class BackboneEngine:
     def step_count(self, t: int):  # checkpoint resume: host value -> device counter
         self._step_count, self._steps_unsure = int(t), False
         self.dev_step.fill_(int(t))
-        self.dev_draw.fill_(int(t))  # one draw per step in the engine-owned loop: a resumed run continues the same mask stream
+        # one draw per forward in the engine-owned loop, set_grad_accum(N) forwards per optimizer step: a resumed run continues the
+        # same mask stream
+        self.dev_draw.fill_(int(t) * self._accum_n)
 
     def set_param_groups(self, groups=None):
         """Parameter groups of the fused Adam (torch.optim.Adam over several groups: eval/test.py:76-84 gives every parameter its own).
@@ -1271,6 +1279,7 @@ class BackboneEngine:
         checkpoint writers raise.  An eval-step replay repacks inside the graph, so it evaluates whatever is in flat_p."""
         if self.flat_ema is None:
             raise RuntimeError("swap_ema: the parameter average was never enabled (set_ema)")
+        self._not_mid_cycle("swap_ema")
         self.call("dpc_arena_swap", self.flat_p, self.flat_ema, self.numel)
         self._ema_swapped = not self._ema_swapped
         self.packed_for_step = -1
@@ -1583,6 +1592,111 @@ class BackboneEngine:
         self.call("dpc_adam_dev", self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.numel, self.lr, 0.9, 0.999, 1e-8,
                   self.wd, self.dev_bc, grad_scale)
 
+    # ------------------------------------------------------------------ gradient accumulation (csrc/grad_accum.hip)
+    def set_grad_accum(self, n: int = 1):
+        """Gradient accumulation in front of the fused step: with n > 1, train_step() -- eager or replayed -- is one MICRO-BATCH, and
+        n of them make one optimizer step.  Micro-batches 0 .. n-2 of a cycle run forward and backward and add flat_g into a second
+        f32 arena, ``flat_acc`` (dpc_grad_accumulate, DPC_ACCUM_ADD): no gradient exchange, no adam_step().  The last one runs
+        forward and backward, turns flat_g into the MEAN gradient of the cycle -- (flat_acc + flat_g) * float32(1 / n), which also
+        returns flat_acc to +0 (DPC_ACCUM_FINISH) -- in front of the gradient exchange, and then adam_step() as it stands: the
+        guard's norm and verdict, the clip, AdamW, LAMB's ratios, the parameter average and the schedule see the mean gradient and
+        count optimizer steps, not micro-batches.  ``self.result`` is every micro-batch's own.  n = 1 (the default) turns it off:
+        train_step(), adam_step() and the captures then run what they ran without it.
+
+        A non-finite value in any micro-gradient reaches the sum, so with skip_nonfinite the whole cycle is dropped (flat_acc is
+        +0 again all the same).  Dropout is keyed on dev_draw, which advances per forward: every micro-batch draws new masks.
+        BatchNorm uses each micro-batch's own statistics (LC's running buffers move once per micro-batch, as in torch), and the
+        contrastive negatives stay those of one micro-batch: accumulation enlarges the optimizer's batch, not the number of negatives.
+
+        With parameter groups only the units of active segments are accumulated (the live-unit rule of the gradient guard): the slices
+        of a frozen parameter are neither read nor written in either arena.
+
+        ``flat_acc`` is allocated zero-filled at the first n > 1 -- before a step is captured, a captured step allocates nothing -- and
+        never otherwise.  Refused inside a capture and while a cycle is open (accum_pending != 0; reset_accum() closes one after an
+        exception).  n is among the scalars a captured step bakes in: a replay after it changed raises."""
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"set_grad_accum: n must be at least 1, got {n}")
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.DpcError("set_grad_accum: not while a graph is being captured")
+        self._not_mid_cycle("set_grad_accum")
+        if n > 1:
+            self._accum_alloc()
+        self._accum_n = n
+
+    def _accum_alloc(self):
+        if self.flat_acc is None:
+            if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise L.DpcError("set_grad_accum: enable the accumulation before a step is captured (it allocates its arena)")
+            self.flat_acc = torch.zeros_like(self.flat_g)
+
+    @property
+    def accum_steps(self) -> int:
+        """micro-batches per optimizer step (1: no accumulation)"""
+        return self._accum_n
+
+    @property
+    def accum_pending(self) -> int:
+        """micro-batches of the open cycle already summed into flat_acc (0: at a cycle boundary)"""
+        return self._accum_pos
+
+    def _not_mid_cycle(self, what: str):
+        if self._accum_pos:
+            raise RuntimeError(f"{what}: an accumulation cycle is open ({self._accum_pos} of {self._accum_n} micro-batches are in "
+                               "flat_acc); finish the cycle, or drop it with reset_accum()")
+
+    def reset_accum(self):
+        """drop the open cycle (after an exception): flat_acc back to zero, the position to 0"""
+        if self.flat_acc is not None:
+            self.flat_acc.zero_()
+        self._accum_pos = 0
+
+    def _accum_launch(self, mode: int, begin: int, end: int):
+        """dpc_grad_accumulate over the floats [begin, end) of the two arenas, under the groups' segment table when there is one"""
+        seg, nseg = (self._seg_dev, self._seg_n) if self._groups else (None, 0)
+        self.call("dpc_grad_accumulate", self.flat_acc, self.flat_g, self.numel, begin, end, seg, nseg, mode, 1.0 / self._accum_n)
+
+    def _accum_finish_and_exchange(self, allreduce=None, cut=None):
+        """the last micro-batch's backward, DPC_ACCUM_FINISH in front of each exchange point, the exchange: two FINISH launches with
+        the two-bucket exchange (the tail's inside on_tail_ready, in front of ``allreduce.start``; the first bucket's after the
+        backward, in front of ``allreduce.finish`` -- left out when the backward did not reach the backbone: that bucket is empty),
+        else one over the whole arena.  cut: a captured step's cut (capture_train_step) in place of the exchange's calls"""
+        if allreduce is not None and hasattr(allreduce, "start"):
+            def tail_ready(tail):
+                self._accum_launch(L.ACCUM_FINISH, self.grad_split, self.numel)
+                if cut is None:
+                    allreduce.start(tail)
+                elif self._backward_reaches_backbone():   # (else one cut serves both exchange points, as without accumulation)
+                    cut()
+
+            self.backward(on_tail_ready=tail_ready)
+            head = self._first_bucket()
+            if head.numel():
+                self._accum_launch(L.ACCUM_FINISH, 0, self.grad_split)
+            if cut is None:
+                allreduce.finish(head)
+            else:
+                cut()
+            return
+        self.backward()
+        self._accum_launch(L.ACCUM_FINISH, 0, self.numel)
+        if allreduce is not None:
+            if cut is None:
+                allreduce(self.flat_g)
+            else:
+                cut()
+
+    def _accum_micro_step(self, allreduce=None):
+        """what train_step() runs behind the forward while set_grad_accum(n > 1) is on: one micro-batch of the cycle"""
+        if self._accum_pos < self._accum_n - 1:
+            self.backward()
+            self._accum_launch(L.ACCUM_ADD, 0, self.numel)
+            self._accum_pos += 1
+            return
+        self._accum_finish_and_exchange(allreduce)
+        self._accum_pos = 0
+        self.adam_step()
+
     def _first_bucket(self) -> torch.Tensor:
         """the gradients finished last (stem + layer1): the second bucket of the two-bucket exchange"""
         return self.flat_g[:self.grad_split]
@@ -1615,6 +1729,9 @@ class BackboneEngine:
         # ... and with another update rule than Adam its kind, its flag and its tables (only then)
         if self._opt_kind != "adam":
             base = base + (("optimizer", self._opt_kind, self._opt_x1d, self._opt_host),)
+        # ... and with gradient accumulation the micro-batches per optimizer step (only then)
+        if self._accum_n > 1:
+            base = base + (("accum", self._accum_n),)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
@@ -1734,7 +1851,9 @@ class BackboneEngine:
         (layer1 + stem backward) -> allreduce.finish(head) + join -> graph C (Adam).  With a backward that stops in front of the
         backbone (_backward_reaches_backbone) there is nothing between the two exchange points, so the capture is cut ONCE: graph A
         (forward, head backward) -> allreduce.start(tail) -> allreduce.finish(empty first bucket), as the eager step does -> graph
-        B (Adam).  No empty hipGraph is created or replayed."""
+        B (Adam).  No empty hipGraph is created or replayed.
+
+        Under set_grad_accum(n > 1) the replay is one MICRO-BATCH per call and holds two such captures (_capture_accum_step)."""
         buf = self.x_s2d if block is None else block   # the static buffer the step reads its input from
         need_backbone = self._backward_reaches_backbone()
         key = (buf.data_ptr(), tuple(buf.shape), id(allreduce) if allreduce is not None else None, self.reserve_cus, tuple(sorted(self.side_off)),
@@ -1776,9 +1895,69 @@ class BackboneEngine:
             eng.packed_for_step = -1
             return result
 
+        if self._accum_n > 1:   # one micro-batch per replay: two captures, picked by the position in the cycle
+            return self._capture_accum_step(key, block, buf, allreduce, warmup, refill, run)
         # block=buf: the static input buffer stays alive (and its address un-reused) as long as the capture does
         return self._capture(key, "train", "capture_train_step() again (it captures a new step for the new values)", warm, body, run,
                              refill, block=buf)
+
+    def _capture_accum_step(self, key: tuple, block, buf, allreduce, warmup: int, refill, run_last):
+        """capture_train_step() under set_grad_accum(n > 1).  The replay is still one micro-batch per call, refill included, and holds
+        two captures taken at the same time: ``replay.micro``, one graph -- refill, forward, backward, DPC_ACCUM_ADD --, and
+        ``replay.last``, the cut protocol of capture_train_step with the DPC_ACCUM_FINISH launches in front of each exchange point
+        (_accum_finish_and_exchange).  It picks by the engine's position in the cycle and advances it, so eager micro-batches and
+        replays may alternate.  The warm-up runs whole cycles and needs a cycle boundary."""
+        hit = self._captures.get(key)
+        if hit is not None:
+            return hit
+        n, result = self._accum_n, self.result
+        again = "capture_train_step() again (it captures a new step for the new values)"
+        if warmup and self._accum_pos:
+            raise RuntimeError("capture_train_step: a warm-up under gradient accumulation runs whole cycles and must start at a cycle "
+                               f"boundary ({self._accum_pos} of {n} micro-batches are pending)")
+
+        def warm():
+            for _ in range(warmup * n):
+                self.train_step(block, allreduce=allreduce)
+
+        def body_micro(cut):
+            self._forward_loss(block, True)
+            self.backward()
+            self._accum_launch(L.ACCUM_ADD, 0, self.numel)
+
+        def run_micro(eng, graphs):
+            eng._not_swapped("replay of a captured train step")
+            graphs[0].replay()
+            return result
+
+        def body_last(cut):
+            self._forward_loss(block, True)
+            self._accum_finish_and_exchange(allreduce, cut)
+            host_steps, unsure = self._step_count, self._steps_unsure
+            self.adam_step()
+            self._step_count, self._steps_unsure = host_steps, unsure  # capture executes nothing
+
+        micro = self._capture(key + ("micro",), "train", again, warm, body_micro, run_micro, refill, block=buf)
+        last = self._capture(key + ("last",), "train", again, lambda: None, body_last, run_last, refill, block=buf)
+        me = weakref.ref(self)
+
+        def replay():
+            eng = me()
+            if eng is None:
+                raise RuntimeError("replay of a captured train step whose engine is gone")
+            if eng._accum_pos < n - 1:
+                res = micro()
+                eng._accum_pos += 1
+            else:
+                res = last()
+                eng._accum_pos = 0
+            return res
+
+        replay.micro, replay.last = micro, last
+        replay.graphs, replay.kernels = micro.graphs + last.graphs, micro.kernels + last.kernels
+        replay.events, replay.refill, replay.block = (micro.events or []) + (last.events or []), refill, buf
+        self._captures[key] = replay
+        return replay
 
     def capture_eval_step(self, refill=None):
         """Captures one evaluation step on the stem's operand (and LC's labels) as they stand -- `refill` (e.g. ``lambda:
@@ -2041,6 +2220,9 @@ class DPCEngine(BackboneEngine):
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""
         self._not_swapped("train_step")
         self._forward_loss(block, True, dropout_masks=dropout_masks)
+        if self._accum_n > 1:   # one micro-batch of the cycle (set_grad_accum)
+            self._accum_micro_step(allreduce)
+            return self.result
         self._backward_and_exchange(allreduce)
         self.adam_step()
         return self.result

@@ -230,6 +230,46 @@ class LambLog:
         return 'LAMB: trust ratio min {:.3g} median {:.3g} max {:.3g}'.format(r[0], median, r[-1])
 
 
+def add_accum_flags(parser):
+    """--accum_steps of both entries (BackboneEngine.set_grad_accum)"""
+    parser.add_argument('--accum_steps', default=1, type=int, metavar='N', help='gradient accumulation inside the fused step: every batch is one '
+                        'micro-batch, N of them make one optimizer step on their mean gradient, with one gradient exchange (works under '
+                        '--graph and --resident).  An epoch runs (batches // N) * N batches; --total_steps, --warmup_steps, --lr_milestones, '
+                        'the "Grad guard:" line and the checkpoint\'s step count are in optimizer steps.  BatchNorm statistics and the '
+                        'contrastive negatives stay those of one micro-batch.  1 = off')
+
+
+def check_accum_flags(args):
+    """what the entries refuse before they start a rank"""
+    if args.accum_steps < 1:
+        raise ValueError('--accum_steps must be at least 1')
+
+
+def open_accum(eng, args):
+    """turns the accumulation on from the flag: before --resume (which continues the dropout stream at steps x N and compares the file's
+    count with the run's) and before any step is captured"""
+    check_accum_flags(args)
+    if args.accum_steps > 1:
+        eng.set_grad_accum(args.accum_steps)
+
+
+def accum_epoch(args, batches: int):
+    """(batches a training epoch runs, optimizer steps in it): whole cycles only, so that every epoch, validation and checkpoint
+    falls on a cycle boundary; a partial cycle at the end is dropped"""
+    steps = batches // args.accum_steps
+    return steps * args.accum_steps, steps
+
+
+def accum_line(args, batches: int, per_gpu: int, world: int):
+    """what rank 0 prints once about the accumulation, or None without the flag: the output then stays byte for byte what it was"""
+    n = args.accum_steps
+    if n <= 1:
+        return None
+    line = 'Accumulation: {0} micro-batches of {1} per optimizer step (effective batch {2})'.format(n, per_gpu, n * per_gpu * world)
+    dropped = batches - accum_epoch(args, batches)[0]
+    return line + (', {} batches per epoch dropped'.format(dropped) if dropped else '')
+
+
 class StepDriver:
     """The steps of a run, eager or replayed.  Without ``graph`` every step is eager.  With it, per RUN (not per epoch) the first two
     train steps and the first validation step are eager -- they size every lazy buffer --; from then on the engine is asked once

@@ -123,6 +123,7 @@ class LCEngine(BackboneEngine):
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         self._not_swapped("state_dict")
+        self._not_mid_cycle("state_dict")
         out = {}
         for k in lc_state_dict_keys(self.network, self.num_class, self.widths):
             if k in self.PRM:
@@ -252,6 +253,9 @@ class LCEngine(BackboneEngine):
         target=None: the labels as they stand in ``self.target``"""
         self._not_swapped("train_step")
         self.forward(block, target, train=True, **masks)
+        if self._accum_n > 1:   # one micro-batch of the cycle (set_grad_accum)
+            self._accum_micro_step(allreduce)
+            return self.result
         self._backward_and_exchange(allreduce)
         self.adam_step()
         return self.result

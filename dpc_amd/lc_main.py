@@ -66,7 +66,7 @@ import time
 
 import torch
 
-from .entry import (GuardLog, LambLog, StepDriver, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+from .entry import (GuardLog, LambLog, StepDriver, accum_epoch, accum_line, add_accum_flags, check_accum_flags, open_accum, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
                     check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
@@ -140,6 +140,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_ema_flags(parser)
     add_schedule_flags(parser)
     add_optimizer_flags(parser)
+    add_accum_flags(parser)
     return parser
 
 
@@ -294,6 +295,8 @@ def _worker(rank: int, world: int, args, port: int):
     ema_eval = open_ema(eng, args, rank)
     # the update rule likewise (--optimizer): its kind and tables are baked values too, and --resume compares the file's rule with it
     lamb = LambLog.open(eng, args, rank)
+    # the accumulation likewise (--accum_steps): a baked value, and --resume continues the dropout stream at steps x N
+    open_accum(eng, args)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
 
     def set_lr(mult, saved=None):
@@ -338,6 +341,7 @@ def _worker(rank: int, world: int, args, port: int):
             iteration = int(ck.get('iteration', 0))
             ckpt.load_ema_state(eng, ck, path)
             ckpt.check_optimizer_kind(eng, ck, path)
+            ckpt.check_accum_steps(eng, ck, path)
             if 'lr_schedule' in ck:   # compared once the run's own schedule is known (open_schedule below)
                 resumed = ({'lr_schedule': ck['lr_schedule']}, path)
             if not args.reset_lr and 'optimizer' in ck:
@@ -405,7 +409,7 @@ def _worker(rank: int, world: int, args, port: int):
             src_val = (mk(args.val_frames, args.val_labels, args.val_lengths, 'val', args.val_offsets, 1) if args.val_frames
                        else mk(args.frames, args.labels, args.lengths, 'val', args.offsets, 1))
             # the draw counters are not in the checkpoint: a resumed run derives them from the epochs already run, which is what they were
-            src_train.set_draw(args.start_epoch * len(src_train))
+            src_train.set_draw(args.start_epoch * accum_epoch(args, len(src_train))[0])
             src_val.set_draw(args.start_epoch * len(src_val))
             if src_train.skipped or src_val.skipped:
                 log('{0} training / {1} validation videos skipped (too short for one clip)'.format(src_train.skipped, src_val.skipped), flush=True)
@@ -457,11 +461,15 @@ def _worker(rank: int, world: int, args, port: int):
 
         # The per-step schedule multiplies whatever the epoch schedule (set_lr) has put into eng.lr / the segment table: on before the
         # first capture, and among the baked values, so the captures set_lr asks for after a milestone carry it too
-        lr_tail = open_schedule(eng, args, len(src_train) if src_train is not None else args.synthetic, rank)
+        # a training epoch under --accum_steps N: whole cycles only; the schedule, the guard's line and LAMB's count its optimizer steps
+        n_all = len(src_train) if src_train is not None else args.synthetic
+        n_train, n_opt = accum_epoch(args, n_all)
+        if args.accum_steps > 1:
+            log(accum_line(args, n_all, per_gpu, world), flush=True)
+        lr_tail = open_schedule(eng, args, n_opt, rank)
         if resumed is not None:
             ckpt.check_lr_schedule(eng, *resumed)
         for epoch in range(args.start_epoch, args.epochs):
-            n_train = len(src_train) if src_train is not None else args.synthetic
             feed = src_train.epoch(dev) if src_train is not None and not args.resident else None
             if args.resident:
                 src_train.begin_epoch()   # the epoch's permutation to the device, the cursor to 0: the one host-to-device copy of the epoch
@@ -476,7 +484,7 @@ def _worker(rank: int, world: int, args, port: int):
             if line:
                 log(line, flush=True)
             if guard and rank == 0:
-                log(guard.epoch_line(n_train), flush=True)
+                log(guard.epoch_line(n_opt), flush=True)
             if lamb and rank == 0:
                 log(lamb.epoch_line(), flush=True)
             vl = va = 0.0
@@ -507,6 +515,8 @@ def _worker(rank: int, world: int, args, port: int):
                     state['ema'] = ckpt.ema_entry(eng, state['state_dict'])
                 if eng.optimizer_kind != 'adam':
                     state['optimizer_kind'] = eng.optimizer_kind
+                if eng.accum_steps > 1:
+                    state['accum_steps'] = eng.accum_steps
                 ckpt.save_checkpoint(state, is_best, filename=os.path.join(args.save_dir, 'epoch%s.pth.tar' % str(epoch + 1)))
         log('Training from ep %d to ep %d finished' % (args.start_epoch, args.epochs))
         if probe:
@@ -522,7 +532,8 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
-    check_schedule_flags(args, 0 if args.frames else args.synthetic)
+    check_accum_flags(args)
+    check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)
     world = world_size(args)
     if args.resident and not args.frames:

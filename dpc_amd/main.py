@@ -29,7 +29,7 @@ import time
 
 import torch
 
-from .entry import (GuardLog, LambLog, StepDriver, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
+from .entry import (GuardLog, LambLog, StepDriver, accum_epoch, accum_line, add_accum_flags, check_accum_flags, open_accum, add_optimizer_flags, check_optimizer_flags, average_over_ranks, add_ema_flags, add_guard_flags, add_schedule_flags, check_ema_flags,
                     check_schedule_flags, launch, open_ema, open_rank, open_schedule, world_size)
 
 
@@ -80,6 +80,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_ema_flags(parser)
     add_schedule_flags(parser)
     add_optimizer_flags(parser)
+    add_accum_flags(parser)
     return parser
 
 
@@ -136,6 +137,7 @@ def _worker(rank: int, world: int, args, port: int):
     resumed = None   # (the file's 'lr_schedule' entry, its path): compared once the run's own schedule is known (open_schedule below)
     ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
     lamb = LambLog.open(eng, args, rank)   # --optimizer: before --resume compares the file's rule with the run's, and before any capture
+    open_accum(eng, args)                  # --accum_steps: before --resume continues the dropout stream, and before any capture
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -180,7 +182,7 @@ def _worker(rank: int, world: int, args, port: int):
             src_train, src_val = mk(store, 0), mk(store_val, 1)
             # the draw counters are not in the checkpoint (the engine keeps none of its counters there): a resumed run derives them
             # from the epochs already run, which is what they were
-            src_train.set_draw(args.start_epoch * len(src_train))
+            src_train.set_draw(args.start_epoch * accum_epoch(args, len(src_train))[0])
             src_val.set_draw(args.start_epoch * len(src_val))
             if rank == 0 and (src_train.skipped or src_val.skipped):
                 print('{0} training / {1} validation videos skipped (too short for one clip)'.format(src_train.skipped, src_val.skipped), flush=True)
@@ -198,7 +200,12 @@ def _worker(rank: int, world: int, args, port: int):
     if args.resident:
         refill, refill_val = (lambda: eng.load_resident(src_train)), (lambda: eng.load_resident(src_val))
     guard = GuardLog.open(eng, args)   # before the first capture: the guard's settings are baked into a captured step
-    lr_tail = open_schedule(eng, args, len(src_train) if src_train is not None else args.synthetic, rank)   # before the first capture, like the guard
+    # a training epoch under --accum_steps N: whole cycles only; the schedule, the guard's line and LAMB's count its optimizer steps
+    n_all = len(src_train) if src_train is not None else args.synthetic
+    n_train, n_opt = accum_epoch(args, n_all)
+    if rank == 0 and args.accum_steps > 1:
+        print(accum_line(args, n_all, per_gpu, world), flush=True)
+    lr_tail = open_schedule(eng, args, n_opt, rank)   # before the first capture, like the guard
     if resumed is not None:
         ckpt.check_lr_schedule(eng, *resumed)
     steps = StepDriver(eng, args.graph, allreduce, refill, refill_val)
@@ -211,7 +218,7 @@ def _worker(rank: int, world: int, args, port: int):
         losses, accs = AverageMeter(), [AverageMeter() for _ in range(3)]
         nonlocal iteration
         src = src_train if train else src_val
-        n_batches = len(src) if src is not None else args.synthetic
+        n_batches = n_train if train else (len(src) if src is not None else args.synthetic)
         feed = src.epoch(dev) if src is not None and not args.resident else None
         if args.resident:
             src.begin_epoch()   # the epoch's permutation to the device, the cursor to 0: the one host-to-device copy of the epoch
@@ -239,7 +246,7 @@ def _worker(rank: int, world: int, args, port: int):
         if line and rank == 0:
             print(line, flush=True)
         if train and guard and rank == 0:
-            print(guard.epoch_line(n_batches), flush=True)
+            print(guard.epoch_line(n_opt), flush=True)
         if train and lamb and rank == 0:
             print(lamb.epoch_line(), flush=True)
         return losses.local_avg, accs[0].local_avg, [a.local_avg for a in accs]
@@ -274,7 +281,8 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
-    check_schedule_flags(args, 0 if args.frames else args.synthetic)
+    check_accum_flags(args)
+    check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)
     if args.resident and not args.frames:
         raise SystemExit('--resident holds the --frames array in HBM: --frames is missing')

@@ -372,6 +372,21 @@ int dpc_adam_groups_dev_ex(float* p, const float* g, float* m, float* v, int64_t
                            const dpc_grad_state* state_dev, dpc_stream_t stream);
 int dpc_grad_scale(float* g, int64_t n, const dpc_adam_segment* segments_dev, int32_t n_segments, const dpc_grad_state* state_dev,
                    dpc_stream_t stream);
+/* ---- gradient accumulation in front of the fused step (csrc/grad_accum.hip): several micro-batches per optimizer step.  `acc` is a
+ * second f32 arena of the size and alignment of the gradient arena `g`, +0 at the start of every cycle:
+ *   DPC_ACCUM_ADD     acc[i] = acc[i] + g[i]; g is only read.
+ *   DPC_ACCUM_FINISH  g[i] = (acc[i] + g[i]) * scale, then acc[i] = +0.0f: one f32 add, rounded, then one f32 multiply, rounded
+ *                     (never an fma).  scale = float32(1 / N), formed on the host.  Every cycle ends with acc back at +0, so there is
+ *                     no "store" mode: every non-final micro-batch is the same launch with the same arguments.
+ * Only the floats of [begin, end) (both multiples of 4, inside [0, n)) are touched; with a dpc_adam_segment table, of those only the
+ * 16-byte units inside an active segment (the live-unit rule of dpc_grad_sumsq): every other unit is neither loaded nor stored, in
+ * either arena.  One writer per value, no atomics.  begin == end is a successful no-op.  DPC_ERR_ARG, and no launch, for: a null or
+ * misaligned arena, acc == g, n <= 0 or n % 4, begin / end not multiples of 4, begin > end, end > n, another mode, a non-finite scale,
+ * a table with a count outside 1..DPC_ADAM_MAX_SEGMENTS. */
+#define DPC_ACCUM_ADD 0
+#define DPC_ACCUM_FINISH 1
+int dpc_grad_accumulate(float* acc, float* g, int64_t n, int64_t begin, int64_t end, const dpc_adam_segment* segments_dev,
+                        int32_t n_segments, int32_t mode, float scale, dpc_stream_t stream);
 /* ---- EMA of the parameters inside the fused step (csrc/loss.hip): dpc_adam_dev_ex / dpc_adam_groups_dev_ex (state_dev nullable, as
  * there) with one more f32 arena, `ema`, updated by the thread that has just updated the 16-byte unit of p:
  *     e += (1 - d) * (p_new - e),   d = min(decay, (float)(1 + t) / (float)(10 + t)),   t = step_dev[0]
