@@ -109,6 +109,19 @@ class LrState(C.Structure):
     _fields_ = [("mult", C.c_float), ("k", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class NegqState(C.Structure):
+    """struct dpc_negq_state (include/dpc_hip.h): the negative queue's record, in device memory"""
+    _fields_ = [("pushes", C.c_int32), ("filled", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+NEGQ_MAX_SLOTS = 64   # DPC_NEGQ_MAX_SLOTS
+
+
+def negq_pitch(R: int) -> int:
+    """DPC_NEGQ_PITCH (include/dpc_hip.h): rows of one slot of the ring"""
+    return (R + 63) // 64 * 64
+
+
 class ConvEpilogue(C.Structure):
     """struct dpc_conv_epilogue (include/dpc_hip.h)"""
     _fields_ = [(n, C.c_void_p) for n in ("addend", "addend_mask", "bn_raw", "bn_mask", "bn_mean", "bn_invstd", "stats")]
@@ -222,6 +235,13 @@ _SIGS = {
     "dpc_score_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     "dpc_score_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp],
     "dpc_ce_finalize": [_vp, _i32, _vp, _vp],
+    "dpc_negq_ws_floats": [_i32, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)],
+    "dpc_negq_push": [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "dpc_negq_clear": [_vp, _vp, _vp],
+    "dpc_negq_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp, _vp],
+    "dpc_negq_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    "dpc_ce_topk_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "dpc_ce_topk_bf16_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "dpc_bn_finalize_running": [_vp, _i32, _i32, _f64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp],
     "dpc_bn_eval_coeffs": [_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_relu_tpool_fwd": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],

@@ -207,10 +207,19 @@ def check_accum_steps(eng, ck: dict, path: str) -> None:
                       f"with {eng.accum_steps}")
 
 
+def check_neg_queue(eng, ck: dict, path: str) -> None:
+    """the negative queue is not in the file (it refills in K batches) and a resumed run takes its K from the flags or the caller; one
+    warning if the file was written under another K.  A file without the entry (every run's without the queue) counts as 0."""
+    k = int(getattr(eng, "neg_queue", 0))
+    if int(ck.get("neg_queue", 0)) != k:
+        warnings.warn(f"{path} was written with a negative queue of {int(ck.get('neg_queue', 0))} batches, this run continues with {k}")
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
     """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
     schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
-    rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'.  Refused while an
+    rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'; with the negative queue on,
+    plus 'neg_queue' (its slot count -- the bank is not in the file).  Refused while an
     accumulation cycle is open: the sum so far is not part of the file"""
     eng._not_swapped("build_state")
     eng._not_mid_cycle("build_state")
@@ -224,6 +233,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
         state["optimizer_kind"] = eng.optimizer_kind
     if eng.accum_steps > 1:
         state["accum_steps"] = eng.accum_steps
+    if getattr(eng, "neg_queue", 0) > 0:   # the slot count only: the bank itself is never written
+        state["neg_queue"] = eng.neg_queue
     return state
 
 
@@ -288,6 +299,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
     load_ema_state(eng, ck, path)
     check_optimizer_kind(eng, ck, path)
     check_accum_steps(eng, ck, path)
+    check_neg_queue(eng, ck, path)   # (load_params above has emptied the bank)
     if check_schedule:
         check_lr_schedule(eng, ck, path)
     info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}

@@ -49,10 +49,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // one workgroup per score row; three L2-resident sweeps (max, sum-exp + rank, gradient)
-template <class TD>
-__global__ __launch_bounds__(256) void ce_row_kernel(const float* score, int rows, int cols, int ld, float* row_ws,
-                                                     TD* dscore, int ld_d) {
-    __shared__ float sh[8];
+// EXT (dpc_ce_topk_ext, and the same arm of the two kernels below): the negative queue's per-row statistics qstats[row] = (m_q, l_q,
+// rk_q, -) are folded in before the exponentials -- mx = max(mx, m_q), se += l_q exp(m_q - mx), rk += rk_q -- and lse_out[row] =
+// log(se) + mx is kept for the queue's backward.  The kernels of the older entries are the EXT = false bodies: the lines they ran.
+template <class TD, bool EXT>
+__device__ __forceinline__ void ce_row_body(float* sh, const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d,
+                                            const float* qstats, float* lse_out) {
     const int row = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* s = score + (long long)row * ld;
@@ -65,6 +67,11 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float* score, int row
     mx = sh[0];
     DPC_UNROLL
     for (int w = 1; w < 4; ++w) mx = sh[w] > mx ? sh[w] : mx;
+    float mq = 0.f, lq = 0.f, rkq = 0.f;
+    if constexpr (EXT) {
+        mq = qstats[4 * (long long)row]; lq = qstats[4 * (long long)row + 1]; rkq = qstats[4 * (long long)row + 2];
+        mx = mq > mx ? mq : mx;
+    }
     float se = 0.f, rk = 0.f;
     for (int j = tid; j < cols; j += 256) {
         const float v = s[j];
@@ -78,9 +85,14 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float* score, int row
     __syncthreads();
     se = sh[0] + sh[1] + sh[2] + sh[3];
     rk = sh[4] + sh[5] + sh[6] + sh[7];
+    if constexpr (EXT) {
+        se += lq * expf(mq - mx);
+        rk += rkq;
+    }
     if (tid == 0) {
         row_ws[2 * row + 0] = logf(se) + mx - tgt;
         row_ws[2 * row + 1] = rk;
+        if constexpr (EXT) lse_out[row] = logf(se) + mx;
     }
     if (dscore) {
         const float inv = 1.f / se, invr = 1.f / (float)rows;
@@ -93,15 +105,27 @@ __global__ __launch_bounds__(256) void ce_row_kernel(const float* score, int row
         for (int j = cols + tid; j < ld_d; j += 256) d[j] = Elt<TD>::from_f32(0.f);
     }
 }
+template <class TD>
+__global__ __launch_bounds__(256) void ce_row_kernel(const float* score, int rows, int cols, int ld, float* row_ws,
+                                                     TD* dscore, int ld_d) {
+    __shared__ float sh[8];
+    ce_row_body<TD, false>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, nullptr, nullptr);
+}
+template <class TD>
+__global__ __launch_bounds__(256) void ce_row_ext_kernel(const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d,
+                                                         const float* qstats, float* lse_out) {
+    __shared__ float sh[8];
+    ce_row_body<TD, true>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, qstats, lse_out);
+}
 
 // The same row kernel with the row held in REGISTERS (NV float4 per thread: one HBM read of the logits instead of three sweeps),
 // 16-byte loads, one exponential per logit (kept for the gradient), 8/16-byte gradient stores.  Needs cols % 4 == 0, 16-byte
 // aligned rows and cols <= 1024 NV; anything else takes ce_row_kernel.  FAST: v_exp_f32 (2^x, ~1 ulp) instead of libm expf --
 // the throughput mode (bf16 gradient); the f32 parity mode keeps the exact form bit for bit.
 // Measured at R = 6 144: ce_row_kernel 117 us for 151 MB of logits + 75 MB of gradient (1.9 TB/s).
-template <class TD, int NV, bool FAST>
-__global__ __launch_bounds__(256) void ce_row_vec_kernel(const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d) {
-    __shared__ float sh[8];
+template <class TD, int NV, bool FAST, bool EXT>
+__device__ __forceinline__ void ce_row_vec_body(float* sh, const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d,
+                                                const float* qstats, float* lse_out) {
     const int row = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* s = score + (long long)row * ld;
@@ -124,6 +148,11 @@ __global__ __launch_bounds__(256) void ce_row_vec_kernel(const float* score, int
     mx = sh[0];
     DPC_UNROLL
     for (int w = 1; w < 4; ++w) mx = sh[w] > mx ? sh[w] : mx;
+    float mq = 0.f, lq = 0.f, rkq = 0.f;
+    if constexpr (EXT) {
+        mq = qstats[4 * (long long)row]; lq = qstats[4 * (long long)row + 1]; rkq = qstats[4 * (long long)row + 2];
+        mx = mq > mx ? mq : mx;
+    }
     float se = 0.f, rk = 0.f;
     const float nm = -mx * 1.4426950408889634f;
     DPC_UNROLL
@@ -145,9 +174,14 @@ __global__ __launch_bounds__(256) void ce_row_vec_kernel(const float* score, int
     __syncthreads();
     se = sh[0] + sh[1] + sh[2] + sh[3];
     rk = sh[4] + sh[5] + sh[6] + sh[7];
+    if constexpr (EXT) {
+        se += lq * (FAST ? fast_exp2((mq - mx) * 1.4426950408889634f) : expf(mq - mx));
+        rk += rkq;
+    }
     if (tid == 0) {
         row_ws[2 * row + 0] = logf(se) + mx - tgt;
         row_ws[2 * row + 1] = rk;
+        if constexpr (EXT) lse_out[row] = logf(se) + mx;
     }
     if (dscore) {
         const float inv = 1.f / se, invr = 1.f / (float)rows;
@@ -175,15 +209,26 @@ __global__ __launch_bounds__(256) void ce_row_vec_kernel(const float* score, int
         for (int j = cols + tid; j < ld_d; j += 256) d[j] = Elt<TD>::from_f32(0.f);
     }
 }
+template <class TD, int NV, bool FAST>
+__global__ __launch_bounds__(256) void ce_row_vec_kernel(const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d) {
+    __shared__ float sh[8];
+    ce_row_vec_body<TD, NV, FAST, false>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, nullptr, nullptr);
+}
+template <class TD, int NV, bool FAST>
+__global__ __launch_bounds__(256) void ce_row_vec_ext_kernel(const float* score, int rows, int cols, int ld, float* row_ws, TD* dscore, int ld_d,
+                                                             const float* qstats, float* lse_out) {
+    __shared__ float sh[8];
+    ce_row_vec_body<TD, NV, FAST, true>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, qstats, lse_out);
+}
 
 
 // bf16 LOGITS (round 6): the train step never returns its score (engine.train_step), so the materialised score of that path is
 // written and read in the compute dtype -- 75 MB instead of 151 MB at R = 6 144 on each side.  Same one-read row kernel: a thread
 // holds NV 16-byte units of 8 logits; loss, rank and d(loss)/d(score) are those of the ROUNDED logits (the target logit included,
 // so "strictly greater than the target" is decided among values of one precision).
-template <int NV>
-__global__ __launch_bounds__(256) void ce_row_vec16_kernel(const bf16_t* score, int rows, int cols, int ld, float* row_ws, bf16_t* dscore, int ld_d) {
-    __shared__ float sh[8];
+template <int NV, bool EXT>
+__device__ __forceinline__ void ce_row_vec16_body(float* sh, const bf16_t* score, int rows, int cols, int ld, float* row_ws, bf16_t* dscore, int ld_d,
+                                                  const float* qstats, float* lse_out) {
     const int row = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const bf16_t* s = score + (long long)row * ld;
@@ -209,6 +254,11 @@ __global__ __launch_bounds__(256) void ce_row_vec16_kernel(const bf16_t* score, 
     mx = sh[0];
     DPC_UNROLL
     for (int w = 1; w < 4; ++w) mx = sh[w] > mx ? sh[w] : mx;
+    float mq = 0.f, lq = 0.f, rkq = 0.f;
+    if constexpr (EXT) {
+        mq = qstats[4 * (long long)row]; lq = qstats[4 * (long long)row + 1]; rkq = qstats[4 * (long long)row + 2];
+        mx = mq > mx ? mq : mx;
+    }
     float se = 0.f, rk = 0.f;
     const float nm = -mx * 1.4426950408889634f;
     DPC_UNROLL
@@ -230,9 +280,14 @@ __global__ __launch_bounds__(256) void ce_row_vec16_kernel(const bf16_t* score, 
     __syncthreads();
     se = sh[0] + sh[1] + sh[2] + sh[3];
     rk = sh[4] + sh[5] + sh[6] + sh[7];
+    if constexpr (EXT) {
+        se += lq * fast_exp2((mq - mx) * 1.4426950408889634f);
+        rk += rkq;
+    }
     if (tid == 0) {
         row_ws[2 * row + 0] = logf(se) + mx - tgt;
         row_ws[2 * row + 1] = rk;
+        if constexpr (EXT) lse_out[row] = logf(se) + mx;
     }
     if (dscore) {
         const float inv = 1.f / se, invr = 1.f / (float)rows;
@@ -253,6 +308,17 @@ __global__ __launch_bounds__(256) void ce_row_vec16_kernel(const bf16_t* score, 
         }
         for (int j = cols + tid; j < ld_d; j += 256) d[j] = Elt<bf16_t>::from_f32(0.f);
     }
+}
+template <int NV>
+__global__ __launch_bounds__(256) void ce_row_vec16_kernel(const bf16_t* score, int rows, int cols, int ld, float* row_ws, bf16_t* dscore, int ld_d) {
+    __shared__ float sh[8];
+    ce_row_vec16_body<NV, false>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, nullptr, nullptr);
+}
+template <int NV>
+__global__ __launch_bounds__(256) void ce_row_vec16_ext_kernel(const bf16_t* score, int rows, int cols, int ld, float* row_ws, bf16_t* dscore, int ld_d,
+                                                               const float* qstats, float* lse_out) {
+    __shared__ float sh[8];
+    ce_row_vec16_body<NV, true>(sh, score, rows, cols, ld, row_ws, dscore, ld_d, qstats, lse_out);
 }
 
 __global__ __launch_bounds__(256) void ce_finalize_kernel(const float* row_ws, int rows, float* result) {
@@ -318,6 +384,53 @@ extern "C" int dpc_ce_topk_bf16(const void* score, int32_t rows, int32_t cols, i
         DPC_LAUNCH((ce_row_vec16_kernel<4>), dim3(rows), dim3(256), stream, (const bf16_t*)score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d);
     } else {
         DPC_LAUNCH((ce_row_vec16_kernel<8>), dim3(rows), dim3(256), stream, (const bf16_t*)score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d);
+    }
+    DPC_LAUNCH(ce_finalize_kernel, dim3(1), dim3(256), stream, row_ws, rows, result);
+    return dpc_launch_status();
+}
+
+// ---- the same two entries with the negative queue's statistics (include/dpc_hip.h): the dispatch conditions of the entries above, the
+// EXT arm of the row kernel each of them selects
+extern "C" int dpc_ce_topk_ext(const float* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
+                               int32_t dtype_d, int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!score || !row_ws || !result || rows <= 0 || cols < rows || ld < cols || !qstats || !lse_out) return DPC_ERR_ARG;
+    if (dscore && ld_d < cols) return DPC_ERR_ARG;
+    const bool vec = cols % 4 == 0 && ld % 4 == 0 && ((uintptr_t)score % 16) == 0 && cols <= 16384 &&
+                     (!dscore || (ld_d % 4 == 0 && ((uintptr_t)dscore % 16) == 0));
+    if (!dscore || dtype_d == DPC_F32) {
+        if (vec && cols <= 8192) {
+            DPC_LAUNCH((ce_row_vec_ext_kernel<float, 8, false>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (float*)dscore, ld_d, qstats, lse_out);
+        } else if (vec) {
+            DPC_LAUNCH((ce_row_vec_ext_kernel<float, 16, false>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (float*)dscore, ld_d, qstats, lse_out);
+        } else {
+            DPC_LAUNCH((ce_row_ext_kernel<float>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (float*)dscore, ld_d, qstats, lse_out);
+        }
+    } else if (dtype_d == DPC_BF16) {
+        if (vec && cols <= 8192) {
+            DPC_LAUNCH((ce_row_vec_ext_kernel<bf16_t, 8, true>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d, qstats, lse_out);
+        } else if (vec) {
+            DPC_LAUNCH((ce_row_vec_ext_kernel<bf16_t, 16, true>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d, qstats, lse_out);
+        } else {
+            DPC_LAUNCH((ce_row_ext_kernel<bf16_t>), dim3(rows), dim3(256), stream, score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d, qstats, lse_out);
+        }
+    } else {
+        return DPC_ERR_ARG;
+    }
+    DPC_LAUNCH(ce_finalize_kernel, dim3(1), dim3(256), stream, row_ws, rows, result);
+    return dpc_launch_status();
+}
+
+extern "C" int dpc_ce_topk_bf16_ext(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
+                                    int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!score || !row_ws || !result || rows <= 0 || cols < rows || ld < cols || !qstats || !lse_out) return DPC_ERR_ARG;
+    if (dscore && ld_d < cols) return DPC_ERR_ARG;
+    if (cols % 8 || ld % 8 || ((uintptr_t)score % 16) || cols > 16384 || (dscore && (ld_d % 8 || ((uintptr_t)dscore % 16)))) return DPC_ERR_UNSUPPORTED;
+    if (cols <= 2048 * 4) {
+        DPC_LAUNCH((ce_row_vec16_ext_kernel<4>), dim3(rows), dim3(256), stream, (const bf16_t*)score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d, qstats, lse_out);
+    } else {
+        DPC_LAUNCH((ce_row_vec16_ext_kernel<8>), dim3(rows), dim3(256), stream, (const bf16_t*)score, rows, cols, ld, row_ws, (bf16_t*)dscore, ld_d, qstats, lse_out);
     }
     DPC_LAUNCH(ce_finalize_kernel, dim3(1), dim3(256), stream, row_ws, rows, result);
     return dpc_launch_status();

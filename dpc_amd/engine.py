@@ -158,6 +158,10 @@ def algorithmic_cost(name, args):
         return 2.0 * args[2] * args[2] * args[3], float(2 * args[2] * args[3] * 2)
     if name == "dpc_score_bwd":            # own, oth, othT, ldT, R, D, ...: one R x R x D contraction (the recompute is not counted)
         return 2.0 * args[4] * args[4] * args[5], float(2 * args[4] * args[5] * 2 + args[4] * args[5] * 4)
+    if name == "dpc_negq_fwd":             # pred, ring, state, R, D, K, ...: R x (K R) x D against a FULL bank (the live share is on the device)
+        return 2.0 * args[3] * args[3] * args[5] * args[4], float((1 + args[5]) * args[3] * args[4] * 2)
+    if name == "dpc_negq_bwd":             # pred, ring, ringT, state, R, D, K, ...: the same contraction (the recompute is not counted)
+        return 2.0 * args[4] * args[4] * args[6] * args[5], float((1 + 2 * args[6]) * args[4] * args[5] * 2 + args[4] * args[5] * 4)
     if name in ("dpc_gemm_nt_splitk", "dpc_gemm_tn_splitk"):       # dtype, M, N, K, A, lda, B, ldb, part, nsplit
         e = _esz(args[0])
         return 2.0 * args[1] * args[2] * args[3], float((args[1] + args[2]) * args[3] * e + args[1] * args[2] * 4)
@@ -544,6 +548,7 @@ class BackboneEngine:
         self._opt_kind, self._opt_x1d, self._opt_key, self._opt_host = "adam", False, None, b""   # update rule of the fused step (set_optimizer)
         self._lamb, self._aw_seg_dev, self._aw_seg_n = None, None, 0   # LAMB's device tables; AdamW's own segment table under exclude_1d
         self._accum_n, self._accum_pos, self.flat_acc = 1, 0, None   # gradient accumulation in front of the fused step (set_grad_accum)
+        self._negq, self._negq_gen = 0, 0   # slots of the negative queue (DPCEngine.set_neg_queue; 0: off) and how often its ring was allocated
         self.seg_uploads = 0          # host-to-device copies of the segment table so far
         self.no_grad_params = frozenset()   # parameters whose gradient nobody wants (requires_grad = False at the module boundary)
         self.seed = int(seed)  # dropout stream (the reference seeds the device generator with 233, dpc/model_3d.py:18); per rank
@@ -1560,6 +1565,12 @@ class BackboneEngine:
                       self.wd, self.dev_bc, grad_scale, st, self.flat_ema, self.dev_step, self._ema)
 
     def adam_step(self, grad_scale: float = 1.0):
+        self._adam_step(grad_scale)
+        # a step (or cycle) the guard skips empties the negative queue: one one-thread launch behind the verdict, only while both are on
+        if self._negq and self._guard is not None and self._guard[1]:
+            self.call("dpc_negq_clear", self._negq_state, self._guard_state)
+
+    def _adam_step(self, grad_scale: float):
         self._not_swapped("adam_step")
         self._count_step()
         if self._opt_kind != "adam":
@@ -1606,7 +1617,8 @@ class BackboneEngine:
         A non-finite value in any micro-gradient reaches the sum, so with skip_nonfinite the whole cycle is dropped (flat_acc is
         +0 again all the same).  Dropout is keyed on dev_draw, which advances per forward: every micro-batch draws new masks.
         BatchNorm uses each micro-batch's own statistics (LC's running buffers move once per micro-batch, as in torch), and the
-        contrastive negatives stay those of one micro-batch: accumulation enlarges the optimizer's batch, not the number of negatives.
+        contrastive negatives stay those of one micro-batch: accumulation enlarges the optimizer's batch, not the number of negatives
+        (DPCEngine.set_neg_queue does that: under it every micro-batch also competes against the keys of the K batches before it).
 
         With parameter groups only the units of active segments are accumulated (the live-unit rule of the gradient guard): the slices
         of a frozen parameter are neither read nor written in either arena.
@@ -1732,6 +1744,11 @@ class BackboneEngine:
         # ... and with gradient accumulation the micro-batches per optimizer step (only then)
         if self._accum_n > 1:
             base = base + (("accum", self._accum_n),)
+        # ... and with the negative queue its slot count (only then)
+        if self._negq:
+            base = base + (("negq", self._negq),)
+            if self._negq_gen > 1:   # ... and which allocation of the ring: a step captured on an earlier one must not replay on this one
+                base = base + (("negq_ring", self._negq_gen),)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
@@ -2059,6 +2076,10 @@ class DPCEngine(BackboneEngine):
         self.d_pred = self.empty((B, P, SQ, D), f32)
         self.d_finf = self.empty((B, P, SQ, D), f32)
         self.mask: Optional[torch.Tensor] = None
+        self._score_path = score_path
+        self._negq_live = False   # the last forward read the negative queue (set_neg_queue): its backward adds the queue part and pushes
+        self._negq_state = self._negq_ring = self._negq_ringT = self._negq_stats = self._negq_lse = self._negq_ws = None
+        self._negq_retired = []   # buffers of an earlier ring that a captured step may still address (set_neg_queue)
         self._need_wgrad(R, R, D)
         nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
         self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
@@ -2076,12 +2097,14 @@ class DPCEngine(BackboneEngine):
             setattr(gd, name, t.data_ptr())
 
     def forward(self, block: torch.Tensor, train: bool = False, dropout_masks: Optional[torch.Tensor] = None,
-                materialise: bool = True, new_draw: bool = True):
+                materialise: bool = True, new_draw: bool = True, use_neg_queue: bool = False):
         """block [B,N,3,SL,H,W] f32 on the device.  Returns the score tensor [B,P,SQ,B,P,SQ] (f32, engine-owned).
         dropout_masks: optional [n_steps,M,D] pre-scaled keep masks (tests); train=True draws them on the device.
         new_draw=False repeats the previous forward's Philox masks (tests comparing two paths on one step).
         materialise=False (bf16 mode): the score is consumed tile by tile by the fused loss (csrc/score_fused.hip) and
-        never written; the return value is None and loss_topk() / backward() use the fused path."""
+        never written; the return value is None and loss_topk() / backward() use the fused path.
+        use_neg_queue: the engine-owned training step's forward (_forward_loss(train=True)) -- with set_neg_queue(K > 0) the rows also
+        compete against the bank's keys, and this forward's backward pushes feat_inf; everything else leaves the bank alone."""
         B, N, P, SQ, D, M = self.B, self.N, self.P, self.SQ, self.D, self.M
         if block is not None:
             if tuple(block.shape) != (B, N, 3, self.SL, self.size, self.size) or block.dtype != torch.float32:
@@ -2117,15 +2140,26 @@ class DPCEngine(BackboneEngine):
             self.score_mode = "fused"
             return None
         self._score16_live = bool(self.score16 is not None and not materialise)
+        # the negative queue: only the engine-owned training step (_forward_loss(train=True)) reads it
+        self._negq_live = bool(self._negq and use_neg_queue)
         if self._score16_live:   # nobody reads the score but the loss: logits in the compute dtype
             self.score_mode = "materialised (bf16 logits)"
             with self.tag("score"):
                 self.gemm(self.pred, self.feat_inf, self.score16, R, R, D, out_f32=False)
+                if self._negq_live:
+                    self._negq_forward(self.score16, L.BF16)
             return None
         self.score_mode = "materialised"
         with self.tag("score"):
             self.gemm(self.pred, self.feat_inf, self.score, R, R, D)
+            if self._negq_live:
+                self._negq_forward(self.score, L.F32)
         return self.score.view(B, P, SQ, B, P, SQ)
+
+    def _negq_forward(self, score: torch.Tensor, dtype_code: int):
+        """per-row (max, sum-exp, rank) of pred against the live keys; the target logit is the diagonal of the in-batch logits"""
+        self.call("dpc_negq_fwd", self.pred, self._negq_ring, self._negq_state, self.R, self.D, self._negq, score, self.R + 1, dtype_code,
+                  self._negq_stats, self._negq_ws)
 
     def get_mask(self) -> torch.Tensor:
         if self.mask is None:
@@ -2140,6 +2174,15 @@ class DPCEngine(BackboneEngine):
         R = self.R
         if self._score_fused:  # per-row (loss term, rank) pairs are already there; d/dscore is recomputed inside the backward
             self.call("dpc_ce_finalize", self.row_ws, R, self.result)
+            return self.result
+        if self._negq_live:   # the same row kernels with the queue's statistics folded in (csrc/loss.hip: the EXT arms)
+            with self.tag("score"):
+                if self._score16_live:
+                    self.call("dpc_ce_topk_bf16_ext", self.score16, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              self.ld_d, self._negq_stats, self._negq_lse)
+                else:
+                    self.call("dpc_ce_topk_ext", self.score, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              L.dtype_code(self.cdtype), self.ld_d, self._negq_stats, self._negq_lse)
             return self.result
         if self._score16_live:
             self.call("dpc_ce_topk_bf16", self.score16, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None, self.ld_d)
@@ -2190,6 +2233,16 @@ class DPCEngine(BackboneEngine):
                     self.call("dpc_reduce_unpack", self.part, ns.value, self.d_finf, R, 1, D, D, 0, 1, 0)
                 else:
                     self.gemm_tn(self.dscore, self.ld_d, self.pred, D, self.d_finf, R, R, D)
+                if self._negq_live and dscore_external is None:
+                    # the queue's share of d_pred, summed behind the in-batch product; d_finf gets nothing (the bank is detached)
+                    n = self.call("dpc_negq_bwd", self.pred, self._negq_ring, self._negq_ringT, self._negq_state, R, D, self._negq,
+                                  self._negq_lse, self._negq_ws)
+                    self.call("dpc_reduce_unpack", self._negq_ws, n, self.d_pred, R, 1, D, D, 0, 1, 1)
+            if self._negq_live and dscore_external is None:
+                # this batch's keys replace the oldest slot -- behind its own backward, so a batch never competes against itself
+                self.call("dpc_negq_push", self.feat_inf, self.finfT, self.ld_d, self._negq_ring, self._negq_ringT, self._negq_state, R, D,
+                          self._negq)
+                self._negq_live = False
         # ---- predict loop + aggregation, reversed: one launch (G_all, dP1, dP2, d_featrelu come back)
         self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
         # ---- temporal pool / split: the backbone's incoming gradient (the main stream's critical path goes on into the backbone)
@@ -2213,8 +2266,86 @@ class DPCEngine(BackboneEngine):
     def _forward_loss(self, block: Optional[torch.Tensor], train: bool, dropout_masks: Optional[torch.Tensor] = None):
         """forward without a score to return (consumed by the loss: bf16 logits, or never written) + CE / top-k.
         dropout_masks: train_step's explicit masks (tests)"""
-        self.forward(block, train=train, dropout_masks=dropout_masks, materialise=False)
+        self.forward(block, train=train, dropout_masks=dropout_masks, materialise=False, use_neg_queue=train)
         self.loss_topk(with_grad=train)
+
+    # ------------------------------------------------------------------ negative queue (csrc/neg_queue.hip)
+    def set_neg_queue(self, k: int = 0):
+        """Keep the keys (``feat_inf``, the encoded future blocks) of the last `k` training batches on the device and use them, detached,
+        as extra negatives of every row of the engine-owned training step (train_step, its accumulation micro-batches, the captured
+        steps): a row then competes against its R in-batch columns and the Q = filled * R keys of the bank.  The loss is the mean of
+        logsumexp(R + Q logits) - target, the printed top-1/3/5 are accuracies among R + Q candidates, d_pred gets both parts, d_finf
+        the in-batch part only, and after its backward the batch's own keys replace the oldest slot.  The in-batch logits are read
+        rounded as before; the queue logits are the f32 accumulators, never materialised (per-row statistics, flash-style).
+
+        A memory bank, not a momentum encoder: the keys are up to `k` updates old.  Evaluation (forward(train=False), validate,
+        capture_eval_step) and the module boundary neither read nor write it.  load_params, checkpoint.resume and reset_neg_queue()
+        empty it; so does a step or cycle the gradient guard skips (skip_nonfinite), so a batch with Inf / NaN features cannot poison
+        the next `k` losses.  The bank is not checkpointed: it refills in `k` batches.  Each rank keeps its own.
+
+        k = 0 turns it off and frees the ring: the step runs the lines it ran.  The current k again only empties the bank; another k
+        allocates a new ring (buffers a captured step may still address are kept alive, and that step's replay raises).  Refused: another compute dtype than bf16, D not 256 or
+        32, score_path="fused", inside a capture, in the middle of an accumulation cycle, k outside 0 .. 64.  k is among the scalars
+        a captured step bakes in."""
+        k = int(k)
+        if k < 0 or k > L.NEGQ_MAX_SLOTS:
+            raise ValueError(f"set_neg_queue: k must be 0 (off) or 1 .. {L.NEGQ_MAX_SLOTS}, got {k}")
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.DpcError("set_neg_queue: not while a graph is being captured")
+        self._not_mid_cycle("set_neg_queue")
+        if k == self._negq:   # nothing to allocate: the bank starts empty all the same
+            self.reset_neg_queue()
+            return
+        if self._negq_ring is not None and self._capture_graphs:
+            # a captured step holds these addresses; its replay raises (the baked scalars changed), but a parked graph must never
+            # point at memory that went back to the allocator
+            self._negq_retired.append((self._negq_state, self._negq_ring, self._negq_ringT, self._negq_stats, self._negq_lse, self._negq_ws))
+        if k == 0:
+            self._negq, self._negq_live = 0, False
+            self._negq_state = self._negq_ring = self._negq_ringT = self._negq_stats = self._negq_lse = self._negq_ws = None
+            return
+        if self.cdtype != torch.bfloat16:
+            raise L.DpcError("set_neg_queue: the negative queue needs the bf16 compute dtype (f32 is the parity mode against a reference "
+                             "that has no bank)")
+        if self.D not in (256, 32):
+            raise L.DpcError(f"set_neg_queue: the feature size must be 256 or 32, not {self.D}")
+        if self._score_path == "fused":
+            raise L.DpcError('set_neg_queue: not with score_path="fused" (the benchmark arm of the in-batch score)')
+        R, D = self.R, self.D
+        pitch = L.negq_pitch(R)
+        nf, nb = C.c_int64(0), C.c_int64(0)
+        self.lib.call("dpc_negq_ws_floats", R, D, k, C.byref(nf), C.byref(nb))
+        self._negq_state = torch.zeros((4,), dtype=torch.int32, device=self.device)
+        self._negq_ring = torch.zeros((k, pitch, D), dtype=self.cdtype, device=self.device)
+        self._negq_ringT = torch.zeros((k, D, pitch), dtype=self.cdtype, device=self.device)
+        self._negq_stats = self.empty((R, 4), torch.float32)
+        self._negq_lse = self.empty((R,), torch.float32)
+        self._negq_ws = self.empty((max(nf.value, nb.value),), torch.float32)
+        self._negq, self._negq_live = k, False
+        self._negq_gen += 1
+
+    @property
+    def neg_queue(self) -> int:
+        """slots of the negative queue (0: off)"""
+        return self._negq
+
+    def neg_queue_filled(self) -> int:
+        """live slots of the bank, read back from the device record (a host synchronisation)"""
+        return int(self._negq_state[1].item()) if self._negq else 0
+
+    def reset_neg_queue(self):
+        """empty the bank: the record back to zero (the ring's contents are dead from then on and never read)"""
+        if self._negq:
+            self._negq_state.zero_()
+        self._negq_live = False
+
+    def release_captures(self):
+        super().release_captures()
+        self._negq_retired.clear()   # no capture of this engine is left to replay on an earlier ring
+
+    def load_params(self, params: Dict[str, torch.Tensor]):
+        super().load_params(params)
+        self.reset_neg_queue()   # keys encoded with other weights are not negatives of these
 
     def train_step(self, block: torch.Tensor, dropout_masks: Optional[torch.Tensor] = None, allreduce=None) -> torch.Tensor:
         """forward + CE/top-k + backward (+ gradient all-reduce) + Adam.  Returns device f32[4] = loss, top1, top3, top5."""

@@ -81,6 +81,10 @@ def build_parser() -> argparse.ArgumentParser:
     add_schedule_flags(parser)
     add_optimizer_flags(parser)
     add_accum_flags(parser)
+    parser.add_argument('--neg_queue', default=0, type=int, metavar='K', help='negative queue: the keys (encoded future blocks) of the last K '
+                        'training batches stay on the GPU and are extra negatives of every training row (engine.set_neg_queue): the loss '
+                        'and the printed training accuracies are then over R + K R candidates.  A memory bank -- keys up to K updates old, '
+                        'no momentum encoder; per GPU; not checkpointed; validation never uses it.  1 .. 64, bf16 only.  0: off')
     return parser
 
 
@@ -138,6 +142,10 @@ def _worker(rank: int, world: int, args, port: int):
     ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
     lamb = LambLog.open(eng, args, rank)   # --optimizer: before --resume compares the file's rule with the run's, and before any capture
     open_accum(eng, args)                  # --accum_steps: before --resume continues the dropout stream, and before any capture
+    if args.neg_queue:                     # --neg_queue: before --resume compares the file's K with the run's, and before any capture
+        eng.set_neg_queue(args.neg_queue)
+        if rank == 0:
+            print('Negative queue: {0} batches ({1} keys of {2}, per GPU)'.format(args.neg_queue, args.neg_queue * eng.R, eng.D), flush=True)
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -277,11 +285,20 @@ def _worker(rank: int, world: int, args, port: int):
         dist.destroy_process_group()
 
 
+def check_neg_queue_flags(args):
+    """--neg_queue, refused before a rank starts"""
+    if args.neg_queue < 0 or args.neg_queue > 64:
+        raise ValueError('--neg_queue must be 0 (off) or 1 .. 64')
+    if args.neg_queue and args.dtype == 'f32':
+        raise ValueError('--neg_queue needs --dtype bf16 (f32 is the parity mode against a reference that has no bank)')
+
+
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
     check_accum_flags(args)
+    check_neg_queue_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)
     if args.resident and not args.frames:

@@ -764,6 +764,45 @@ int dpc_knn_recall(const int32_t* top_idx, int32_t nq, int32_t K, const int64_t*
                    int32_t num_class, const int32_t* ks, int32_t nk, int64_t* hits, int32_t* first_hit, int64_t* confusion,
                    dpc_stream_t stream);
 
+/* ---- negative queue (csrc/neg_queue.hip): the keys (feature_inf) of the last K training batches, kept on the device and used,
+ * detached, as extra negatives of every training row.  bf16 operands, D = 256 or 32, 1 <= K <= DPC_NEGQ_MAX_SLOTS.
+ *   ring   [K][pitch][D] bf16, pitch = DPC_NEGQ_PITCH(R): slot k holds one batch's R keys in its first R rows.
+ *   ringT  [K][D][pitch] bf16: the same keys transposed, the B operand of the backward's second product.
+ *   state  the device record.  Slots fill in order, so slots [0, filled) are live and nothing else is ever read into a result:
+ *          rows / columns >= R of a slot, slots >= filled and everything at filled = 0 may hold anything (NaN included).
+ * Every launch argument is the same every step; what changes (the slot to write, the number of live slots) is read from the record.
+ * No atomics, one writer per value, fixed combine orders: same inputs, same bits. */
+#define DPC_NEGQ_MAX_SLOTS 64
+#define DPC_NEGQ_PITCH(R) (((R) + 63) / 64 * 64)
+typedef struct dpc_negq_state {
+    int32_t pushes;   /* batches pushed since the bank was last empty */
+    int32_t filled;   /* live slots: min(pushes, K) */
+    int32_t reserved[2];
+} dpc_negq_state;           /* 16 bytes, device memory */
+/* floats of `ws` for dpc_negq_fwd / dpc_negq_bwd; returns the backward's slab count (what dpc_negq_bwd returns) */
+int dpc_negq_ws_floats(int32_t R, int32_t D, int32_t K, int64_t* fwd_floats, int64_t* bwd_floats);
+/* finf [R][D] -> slot (pushes % K) of ring, finfT [D][ldT] (columns >= R zero, ldT % 8 == 0, R <= ldT <= pitch) -> the same slot of
+ * ringT; then pushes += 1, filled = min(filled + 1, K).  The slot index is read on the device. */
+int dpc_negq_push(const void* finf, const void* finfT, int32_t ldT, void* ring, void* ringT, dpc_negq_state* state, int32_t R, int32_t D,
+                  int32_t K, dpc_stream_t stream);
+/* one thread: the record back to empty.  guard != NULL: only if the gradient guard's verdict says skip */
+int dpc_negq_clear(dpc_negq_state* state, const dpc_grad_state* guard, dpc_stream_t stream);
+/* stats[R][4] = (m, l, rk, 0) per row of pred over the live keys: m = max s, l = sum exp(s - m), rk = #{s > tgt_i}, s = pred_i . q_c
+ * (f32 accumulators, unrounded); tgt_i = tgt[i * tgt_stride] of dtype tgt_dtype (DPC_F32 / DPC_BF16).  Empty bank: (-1e30, 0, 0). */
+int dpc_negq_fwd(const void* pred, const void* ring, const dpc_negq_state* state, int32_t R, int32_t D, int32_t K, const void* tgt,
+                 int64_t tgt_stride, int32_t tgt_dtype, float* stats, float* ws, dpc_stream_t stream);
+/* out_part[slab][R][D] (f32): partial sums of  sum_c exp(s_ic - lse_i) / R * q_c  over the live keys (dS rounded to bf16); slabs of
+ * dead column ranges are zero.  Returns the slab count; the caller sums the slabs (dpc_reduce_unpack). */
+int dpc_negq_bwd(const void* pred, const void* ring, const void* ringT, const dpc_negq_state* state, int32_t R, int32_t D, int32_t K,
+                 const float* lse, float* out_part, dpc_stream_t stream);
+/* dpc_ce_topk / dpc_ce_topk_bf16 with the queue's per-row statistics qstats[rows][4] (dpc_negq_fwd) folded in before the
+ * exponentials: mx = max(mx_in, m_q), se += l_q exp(m_q - mx), rk += rk_q; lse_out[rows] = log(se) + mx for dpc_negq_bwd.  The same
+ * row kernels and dispatch; with empty statistics row_ws, result and dscore are those of the older entries bit for bit. */
+int dpc_ce_topk_ext(const float* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore, int32_t dtype_d,
+                    int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream);
+int dpc_ce_topk_bf16_ext(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
+                         int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
