@@ -242,6 +242,8 @@ _SIGS = {
     "dpc_negq_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "dpc_ce_topk_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "dpc_ce_topk_bf16_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "dpc_rownorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
+    "dpc_rownorm_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
     "dpc_bn_finalize_running": [_vp, _i32, _i32, _f64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp],
     "dpc_bn_eval_coeffs": [_vp, _vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_relu_tpool_fwd": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],

@@ -215,11 +215,23 @@ def check_neg_queue(eng, ck: dict, path: str) -> None:
         warnings.warn(f"{path} was written with a negative queue of {int(ck.get('neg_queue', 0))} batches, this run continues with {k}")
 
 
+def check_score_norm(eng, ck: dict, path: str) -> None:
+    """the form of the score is part of the model: a file written under another form or temperature than the run's is another model,
+    whose loss and validation numbers do not continue this one's -- an error, not a warning.  A file without the entry (every run's
+    with the dot-product score) counts as ("dot", 1)."""
+    kind, t = getattr(eng, "score_norm", ("dot", 1.0))
+    entry = ck.get("score_norm") or {"kind": "dot", "temperature": 1.0}
+    if entry.get("kind") != kind or float(entry.get("temperature", 1.0)) != float(t):
+        raise ValueError(f"{path} was trained with the {entry.get('kind')} score at temperature {float(entry.get('temperature', 1.0)):g}, "
+                         f"this run scores {kind} at temperature {float(t):g}: a different model (set --score_norm / --temperature, or "
+                         "set_score_norm, to the file's)")
+
+
 def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> dict:
     """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
     schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
     rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'; with the negative queue on,
-    plus 'neg_queue' (its slot count -- the bank is not in the file).  Refused while an
+    plus 'neg_queue' (its slot count -- the bank is not in the file); under the cosine score, plus 'score_norm' ({'kind', 'temperature'}).  Refused while an
     accumulation cycle is open: the sum so far is not part of the file"""
     eng._not_swapped("build_state")
     eng._not_mid_cycle("build_state")
@@ -235,6 +247,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
         state["accum_steps"] = eng.accum_steps
     if getattr(eng, "neg_queue", 0) > 0:   # the slot count only: the bank itself is never written
         state["neg_queue"] = eng.neg_queue
+    if getattr(eng, "score_norm", ("dot", 1.0))[0] != "dot":
+        state["score_norm"] = {"kind": eng.score_norm[0], "temperature": eng.score_norm[1]}
     return state
 
 
@@ -285,6 +299,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
     read from the file: the engine's own is compared with it (check_lr_schedule) -- unless check_schedule is False, for a caller
     that sets its schedule only after the load and compares then."""
     ck = torch.load(path, map_location="cpu", weights_only=False)
+    check_score_norm(eng, ck, path)   # before anything is loaded: a file of another score form leaves the engine as it was
     load_model_state(eng, ck["state_dict"], strict=True)
     if not reset_lr:
         if "optimizer" in ck:

@@ -40,6 +40,7 @@ import torch
 from . import _lib as L
 from .plan import LAYER_PLAN, LAYER_WIDTH, block_geometry, fold_decision, out_shape_of, unit_descs, walk_blocks  # shared with the plan query
 BN_EPS = 1e-5
+SCORE_NORM_EPS = 1e-12   # F.normalize's eps (the cosine score, DPCEngine.set_score_norm)
 
 
 def param_shapes(network: str, widths: Sequence[int] = LAYER_WIDTH) -> "Dict[str, Tuple[int, ...]]":
@@ -1749,6 +1750,9 @@ class BackboneEngine:
             base = base + (("negq", self._negq),)
             if self._negq_gen > 1:   # ... and which allocation of the ring: a step captured on an earlier one must not replay on this one
                 base = base + (("negq_ring", self._negq_gen),)
+        # ... and with the cosine score its form and temperature (only then)
+        if getattr(self, "_snorm", None) is not None:
+            base = base + (("score_norm", "cosine", self._snorm[0]),)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
@@ -2080,6 +2084,9 @@ class DPCEngine(BackboneEngine):
         self._negq_live = False   # the last forward read the negative queue (set_neg_queue): its backward adds the queue part and pushes
         self._negq_state = self._negq_ring = self._negq_ringT = self._negq_stats = self._negq_lse = self._negq_ws = None
         self._negq_retired = []   # buffers of an earlier ring that a captured step may still address (set_neg_queue)
+        self._snorm = None        # the cosine score (set_score_norm): None, or (temperature, float32(1 / temperature))
+        self.pred_n = self.finf_n = self.rnorm = None   # ... its normalised operands [R][D] and the rows' 1 / norm, f32 [2R]
+        self._snorm_retired = []
         self._need_wgrad(R, R, D)
         nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
         self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
@@ -2132,10 +2139,15 @@ class DPCEngine(BackboneEngine):
         self.call("dpc_gru_chain_fwd", C.byref(gd))
         # score (dpc/model_3d.py:79-84): pred [R][D] x feat_inf [R][D]^T
         R = self.R
+        sp, sf = self.pred, self.feat_inf
+        if self._snorm is not None:   # the cosine score: pred / (|pred| T) against feat_inf / |feat_inf|, train and eval alike
+            sp, sf = self.pred_n, self.finf_n
+            with self.tag("score"):
+                self.call("dpc_rownorm_fwd", self.pred, self.feat_inf, sp, sf, self.rnorm, R, D, dc, self._snorm[1], 1.0, SCORE_NORM_EPS)
         self._score_fused = bool(self.score_fusable and not materialise)
         if self._score_fused:
             with self.tag("score"):
-                self.call("dpc_score_fwd", self.pred, self.feat_inf, R, D, self.score_diag, self.score_lse2, self.row_ws, None,
+                self.call("dpc_score_fwd", sp, sf, R, D, self.score_diag, self.score_lse2, self.row_ws, None,
                           self.score_ws)
             self.score_mode = "fused"
             return None
@@ -2145,21 +2157,25 @@ class DPCEngine(BackboneEngine):
         if self._score16_live:   # nobody reads the score but the loss: logits in the compute dtype
             self.score_mode = "materialised (bf16 logits)"
             with self.tag("score"):
-                self.gemm(self.pred, self.feat_inf, self.score16, R, R, D, out_f32=False)
+                self.gemm(sp, sf, self.score16, R, R, D, out_f32=False)
                 if self._negq_live:
                     self._negq_forward(self.score16, L.BF16)
             return None
         self.score_mode = "materialised"
         with self.tag("score"):
-            self.gemm(self.pred, self.feat_inf, self.score, R, R, D)
+            self.gemm(sp, sf, self.score, R, R, D)
             if self._negq_live:
                 self._negq_forward(self.score, L.F32)
         return self.score.view(B, P, SQ, B, P, SQ)
 
     def _negq_forward(self, score: torch.Tensor, dtype_code: int):
         """per-row (max, sum-exp, rank) of pred against the live keys; the target logit is the diagonal of the in-batch logits"""
-        self.call("dpc_negq_fwd", self.pred, self._negq_ring, self._negq_state, self.R, self.D, self._negq, score, self.R + 1, dtype_code,
+        self.call("dpc_negq_fwd", self._score_operands()[0], self._negq_ring, self._negq_state, self.R, self.D, self._negq, score, self.R + 1, dtype_code,
                   self._negq_stats, self._negq_ws)
+
+    def _score_operands(self):
+        """(pred, feat_inf) as the score reads them: the normalised copies under the cosine score (set_score_norm)"""
+        return (self.pred, self.feat_inf) if self._snorm is None else (self.pred_n, self.finf_n)
 
     def get_mask(self) -> torch.Tensor:
         if self.mask is None:
@@ -2208,18 +2224,18 @@ class DPCEngine(BackboneEngine):
             if self.ld_d != R:
                 self.dscore.zero_()
             self.dscore[:, :R].copy_(src)  # module-boundary path only (torch hands over an arbitrary d/dscore)
-        # score = pred @ finf^T  ->  d_pred = dS @ finf ; d_finf = dS^T @ pred
+        # score = pred @ finf^T  ->  d_pred = dS @ finf ; d_finf = dS^T @ pred  (under the cosine score: of the normalised operands)
+        sp, sf = self._score_operands()
         both = self.cdtype == torch.bfloat16 and ((self._score_fused and dscore_external is None) or bool(self._tn_splits))
         if both:   # feature_inf^T and pred^T, one launch
-            self.call("dpc_transpose2d_bf16x2", self.feat_inf, self.pred, D, self.finfT, self.predT, self.ld_d, R, D)
+            self.call("dpc_transpose2d_bf16x2", sf, sp, D, self.finfT, self.predT, self.ld_d, R, D)
         else:
-            self.call("dpc_transpose2d", self.feat_inf, dc, D, self.finfT, dc, self.ld_d, R, D)
+            self.call("dpc_transpose2d", sf, dc, D, self.finfT, dc, self.ld_d, R, D)
         if self._score_fused and dscore_external is None:
             if not both:
-                self.call("dpc_transpose2d", self.pred, dc, D, self.predT, dc, self.ld_d, R, D)
+                self.call("dpc_transpose2d", sp, dc, D, self.predT, dc, self.ld_d, R, D)
             with self.tag("score"):
-                for own, oth, othT, by_owner, out in ((self.pred, self.feat_inf, self.finfT, 1, self.d_pred),
-                                                      (self.feat_inf, self.pred, self.predT, 0, self.d_finf)):
+                for own, oth, othT, by_owner, out in ((sp, sf, self.finfT, 1, self.d_pred), (sf, sp, self.predT, 0, self.d_finf)):
                     n = self.call("dpc_score_bwd", own, oth, othT, self.ld_d, R, D, self.score_lse2, by_owner, self.score_ws)
                     self.call("dpc_reduce_unpack", self.score_ws, n, out, R, 1, D, D, 0, 1, 0)
         else:
@@ -2232,17 +2248,21 @@ class DPCEngine(BackboneEngine):
                     self.call("dpc_gemm_tn_splitk", dc, R, D, R, self.dscore, self.ld_d, self.predT, self.ld_d, self.part, C.byref(ns))
                     self.call("dpc_reduce_unpack", self.part, ns.value, self.d_finf, R, 1, D, D, 0, 1, 0)
                 else:
-                    self.gemm_tn(self.dscore, self.ld_d, self.pred, D, self.d_finf, R, R, D)
+                    self.gemm_tn(self.dscore, self.ld_d, sp, D, self.d_finf, R, R, D)
                 if self._negq_live and dscore_external is None:
                     # the queue's share of d_pred, summed behind the in-batch product; d_finf gets nothing (the bank is detached)
-                    n = self.call("dpc_negq_bwd", self.pred, self._negq_ring, self._negq_ringT, self._negq_state, R, D, self._negq,
+                    n = self.call("dpc_negq_bwd", sp, self._negq_ring, self._negq_ringT, self._negq_state, R, D, self._negq,
                                   self._negq_lse, self._negq_ws)
                     self.call("dpc_reduce_unpack", self._negq_ws, n, self.d_pred, R, 1, D, D, 0, 1, 1)
             if self._negq_live and dscore_external is None:
                 # this batch's keys replace the oldest slot -- behind its own backward, so a batch never competes against itself
-                self.call("dpc_negq_push", self.feat_inf, self.finfT, self.ld_d, self._negq_ring, self._negq_ringT, self._negq_state, R, D,
+                self.call("dpc_negq_push", sf, self.finfT, self.ld_d, self._negq_ring, self._negq_ringT, self._negq_state, R, D,
                           self._negq)
                 self._negq_live = False
+        if self._snorm is not None:   # d_pred / d_finf are final: through the normalisation, in place, back to the raw operands
+            with self.tag("score"):
+                self.call("dpc_rownorm_bwd", self.pred, self.feat_inf, self.rnorm, self.d_pred, self.d_finf, R, D, dc, self._snorm[1], 1.0,
+                          SCORE_NORM_EPS)
         # ---- predict loop + aggregation, reversed: one launch (G_all, dP1, dP2, d_featrelu come back)
         self.call("dpc_gru_chain_bwd", C.byref(self.gru_desc))
         # ---- temporal pool / split: the backbone's incoming gradient (the main stream's critical path goes on into the backbone)
@@ -2339,9 +2359,58 @@ class DPCEngine(BackboneEngine):
             self._negq_state.zero_()
         self._negq_live = False
 
+    # ------------------------------------------------------------------ cosine score (csrc/score_norm.hip)
+    def set_score_norm(self, kind: str = "dot", temperature: float = 1.0):
+        """The form of the contrastive score.  ``"dot"`` (temperature 1) is the reference's pred . feat_inf.  ``"cosine"`` scores
+        L2-normalised operands over a temperature: s = (pred / |pred|) . (feat_inf / |feat_inf|) / T, F.normalize's semantics
+        (eps 1e-12), so every logit lies in [-1/T, 1/T] and keys of different feature scale -- a memory bank's old and new ones --
+        compete on equal terms.  dpc_rownorm_fwd runs behind the recurrence in every forward, train and eval alike (it defines the
+        model's score), writes ``pred_n`` (scaled by float32(1 / T)) and ``finf_n`` and keeps the rows' 1 / norm in ``rnorm``; every
+        consumer of the score operands -- the score contraction of all three routes, the negative queue and what it pushes, the
+        transposes and products of the backward -- reads those; ``pred`` / ``feat_inf`` keep the raw values.  dpc_rownorm_bwd takes
+        d_pred / d_finf back through the normalisation, in place, once both are final and before the recurrence's backward -- on the
+        module boundary's backward(dscore_external) too.  Two launches per training step, one per evaluation step.
+
+        "dot" frees the buffers: the step runs the lines it ran.  Every call empties the negative queue (keys of another geometry are
+        not negatives of this one).  Refused: an unknown kind, "dot" with another temperature than 1, a temperature (or its f32
+        reciprocal) that is not finite and positive, D not 256 or 32, inside a capture, in the middle of an accumulation cycle.  The
+        form and T are among the scalars a captured step bakes in."""
+        if kind not in ("dot", "cosine"):
+            raise ValueError(f"set_score_norm: kind must be 'dot' or 'cosine', got {kind!r}")
+        t = float(temperature)
+        if not (math.isfinite(t) and t > 0):
+            raise ValueError(f"set_score_norm: the temperature must be finite and positive, got {temperature}")
+        if kind == "dot" and t != 1.0:
+            raise ValueError("set_score_norm: a temperature other than 1 needs kind='cosine' (the dot-product score is the reference's)")
+        scale = C.c_float(1.0 / t).value   # float32(1 / T), rounded once, here
+        if not (math.isfinite(scale) and scale > 0):
+            raise ValueError(f"set_score_norm: 1 / temperature is not a finite positive float32 (temperature {temperature})")
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.DpcError("set_score_norm: not while a graph is being captured")
+        self._not_mid_cycle("set_score_norm")
+        if kind == "cosine" and self.D not in (256, 32):
+            raise L.DpcError(f"set_score_norm: the feature size must be 256 or 32, not {self.D}")
+        if self.pred_n is not None and self._capture_graphs and kind == "dot":
+            self._snorm_retired.append((self.pred_n, self.finf_n, self.rnorm))   # a parked graph never points at freed memory
+        self.reset_neg_queue()
+        if kind == "dot":
+            self._snorm = None
+            self.pred_n = self.finf_n = self.rnorm = None
+            return
+        if self.pred_n is None:
+            self.pred_n, self.finf_n = self.empty((self.R, self.D), self.cdtype), self.empty((self.R, self.D), self.cdtype)
+            self.rnorm = self.empty((2 * self.R,), torch.float32)
+        self._snorm = (t, scale)
+
+    @property
+    def score_norm(self):
+        """(kind, temperature) of the score: ("dot", 1.0) or ("cosine", T)"""
+        return ("dot", 1.0) if self._snorm is None else ("cosine", self._snorm[0])
+
     def release_captures(self):
         super().release_captures()
         self._negq_retired.clear()   # no capture of this engine is left to replay on an earlier ring
+        self._snorm_retired.clear()
 
     def load_params(self, params: Dict[str, torch.Tensor]):
         super().load_params(params)

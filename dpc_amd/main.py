@@ -23,6 +23,7 @@ written here resumes in the reference and vice versa (tests/test_checkpoint.py).
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import re
 import time
@@ -85,6 +86,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'training batches stay on the GPU and are extra negatives of every training row (engine.set_neg_queue): the loss '
                         'and the printed training accuracies are then over R + K R candidates.  A memory bank -- keys up to K updates old, '
                         'no momentum encoder; per GPU; not checkpointed; validation never uses it.  1 .. 64, bf16 only.  0: off')
+    parser.add_argument('--score_norm', default='dot', choices=['dot', 'cosine'], help='form of the contrastive score (engine.set_score_norm): '
+                        'dot = pred . feature_inf, the reference\'s; cosine = the L2-normalised operands over --temperature, every logit in '
+                        '[-1/T, 1/T] (training and validation alike).  Another model: loss and accuracies compare between runs of one T only')
+    parser.add_argument('--temperature', default=1.0, type=float, metavar='T', help='temperature of --score_norm cosine (e.g. 0.07); must stay 1 '
+                        'with the dot-product score')
     return parser
 
 
@@ -142,6 +148,10 @@ def _worker(rank: int, world: int, args, port: int):
     ema_eval = open_ema(eng, args, rank)   # before the loads (each re-seeds the average; --resume then reads the file's) and before any capture
     lamb = LambLog.open(eng, args, rank)   # --optimizer: before --resume compares the file's rule with the run's, and before any capture
     open_accum(eng, args)                  # --accum_steps: before --resume continues the dropout stream, and before any capture
+    if args.score_norm != 'dot':           # --score_norm: before --neg_queue (it empties the bank), --resume (it compares the file's) and any capture
+        eng.set_score_norm(args.score_norm, args.temperature)
+        if rank == 0:
+            print('Score: {0}, temperature {1:g}'.format(args.score_norm, args.temperature), flush=True)
     if args.neg_queue:                     # --neg_queue: before --resume compares the file's K with the run's, and before any capture
         eng.set_neg_queue(args.neg_queue)
         if rank == 0:
@@ -293,12 +303,21 @@ def check_neg_queue_flags(args):
         raise ValueError('--neg_queue needs --dtype bf16 (f32 is the parity mode against a reference that has no bank)')
 
 
+def check_score_flags(args):
+    """--score_norm / --temperature, refused before a rank starts"""
+    if not (math.isfinite(args.temperature) and args.temperature > 0):
+        raise ValueError('--temperature must be finite and positive')
+    if args.score_norm == 'dot' and args.temperature != 1.0:
+        raise ValueError('--temperature other than 1 needs --score_norm cosine (the dot-product score is the reference\'s)')
+
+
 def main(argv=None, _simulator=None, _widths=None, _probe=None):
     args = build_parser().parse_args(argv)
     args._simulator, args._widths, args._probe = _simulator, _widths, _probe   # tests/test_entries.py: the CPU tier runs the entry on the simulator
     check_ema_flags(args)
     check_accum_flags(args)
     check_neg_queue_flags(args)
+    check_score_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)
     if args.resident and not args.frames:

@@ -268,9 +268,16 @@ class DPC_RNN(_EngineModule):
     _SAVED_AS = "dpc/main.py:166-174 (dpc_amd.checkpoint writes the reference's dictionary)"
 
     def __init__(self, sample_size, num_seq=8, seq_len=5, pred_step=3, network="resnet50",
-                 compute_dtype=torch.float32, widths=LAYER_WIDTH, seed: int = 0, _simulator: Optional[L.Lib] = None):
+                 compute_dtype=torch.float32, widths=LAYER_WIDTH, seed: int = 0, _simulator: Optional[L.Lib] = None,
+                 score_norm: str = "dot", temperature: float = 1.0):
         super().__init__(sample_size, num_seq, seq_len, network, compute_dtype, widths, _simulator)
         self.pred_step = pred_step
+        # the form of the score (DPCEngine.set_score_norm): "dot", the reference's, or "cosine" over a temperature
+        if score_norm not in ("dot", "cosine"):
+            raise ValueError(f"score_norm must be 'dot' or 'cosine', got {score_norm!r}")
+        if not (math.isfinite(float(temperature)) and float(temperature) > 0) or (score_norm == "dot" and float(temperature) != 1.0):
+            raise ValueError("temperature must be finite and positive, and 1 unless score_norm='cosine'")
+        self.score_norm, self.temperature = score_norm, float(temperature)
         self.mask = None
         self._param_names: List[str] = []
         self._forced_masks = None
@@ -295,8 +302,11 @@ class DPC_RNN(_EngineModule):
 
     def _make_engine(self, B, dev):
         self.mask = None   # the contrastive mask belongs to the engine this one replaces
-        return DPCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, self.pred_step, B, dev,
-                         self.compute_dtype, self.widths, lib=self._simulator)
+        eng = DPCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, self.pred_step, B, dev,
+                        self.compute_dtype, self.widths, lib=self._simulator)
+        if self.score_norm != "dot":
+            eng.set_score_norm(self.score_norm, self.temperature)
+        return eng
 
     def forward(self, block):
         # block: [B, N, C, SL, H, W] (dpc/model_3d.py:47-49)
@@ -334,6 +344,8 @@ class DPC_RNN(_EngineModule):
                     warnings.warn(_REPLICA_NOTE, stacklevel=3)
                 eng = DPCEngine(self.network, self.sample_size, self.num_seq, self.seq_len, self.pred_step, B, dev, self.compute_dtype,
                                 self.widths, lib=self._simulator, seed=233 + slot)   # per-replica dropout stream (dpc/model_3d.py:18 seeds 233)
+                if self.score_norm != "dot":
+                    eng.set_score_norm(self.score_norm, self.temperature)
                 for old_key in [q for q in self._replica_engines if q[:2] == key[:2]]:   # another batch size / dtype on this device: one engine per device
                     del self._replica_engines[old_key]
                 self._replica_engines[key] = eng
@@ -351,7 +363,7 @@ class DPC_RNN(_EngineModule):
         """a fresh module with the same constructor arguments, the same parameter VALUES (clones, not arena views) and no engine --
         it builds its own at its first forward (copy.deepcopy(model): EMA / averaged copies, torch.optim.swa_utils.AveragedModel)"""
         new = type(self)(self.sample_size, self.num_seq, self.seq_len, self.pred_step, self.network, compute_dtype=self.compute_dtype,
-                         widths=self.widths, _simulator=self._simulator)
+                         widths=self.widths, _simulator=self._simulator, score_norm=self.score_norm, temperature=self.temperature)
         new.compute_dtype = self.compute_dtype   # the constructor lets DPC_COMPUTE_DTYPE override its argument; a copy keeps what the original RUNS in
         mine = dict(self.named_parameters())
         with torch.no_grad():

@@ -803,6 +803,20 @@ int dpc_ce_topk_ext(const float* score, int32_t rows, int32_t cols, int32_t ld, 
 int dpc_ce_topk_bf16_ext(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
                          int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream);
 
+/* ---- cosine score (csrc/score_norm.hip): L2 normalisation of the score's two operands in front of the contraction, and its backward.
+ * Rows [R][D] of `dtype` (DPC_F32 / DPC_BF16), D = 256 or 32 (else DPC_ERR_UNSUPPORTED); one launch serves operand a and, when
+ * xb != NULL, operand b (xb and yb / gb are NULL together).  rnorm is f32 [2R]: operand a's rows first, then b's.
+ *   fwd   n = sqrtf(sum x_d^2) (f32), rn = 1 / max(n, eps), y_d = round_to_dtype(x_d * (scale * rn)), rnorm[row] = rn
+ *   bwd   in place on the f32 gradients g [R][D] at y:  u_d = x_d * rn, t = sum g_d u_d,  g_d <- (scale * rn) * (g_d - u_d * t);
+ *         a row the forward clamped (rn >= 1 / eps):  g_d <- (scale * rn) * g_d
+ * F.normalize's semantics times a scale (1 / temperature for pred, 1 for the keys).  Fixed summation order, no atomics, nothing
+ * contracted: same inputs, same bits.  DPC_ERR_ARG: a NULL or misaligned (16 bytes; rnorm 4) pointer, R < 1, a scale or an eps that
+ * is not finite and positive. */
+int dpc_rownorm_fwd(const void* xa, const void* xb, void* ya, void* yb, float* rnorm, int32_t R, int32_t D, int32_t dtype, float scale_a,
+                    float scale_b, float eps, dpc_stream_t stream);
+int dpc_rownorm_bwd(const void* xa, const void* xb, const float* rnorm, float* ga, float* gb, int32_t R, int32_t D, int32_t dtype,
+                    float scale_a, float scale_b, float eps, dpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
