@@ -122,6 +122,29 @@ def negq_pitch(R: int) -> int:
     return (R + 63) // 64 * 64
 
 
+class NegClasses(C.Structure):
+    """struct dpc_neg_classes (include/dpc_hip.h): geometry and class weights of dpc_ce_topk[_bf16]_cls, passed by value"""
+    _fields_ = ([(n, C.c_int32) for n in ("B", "P", "SQ", "flags")] +
+                [(n, C.c_float) for n in ("w_spatial", "w_temporal", "w_easy", "reserved")])
+
+
+NEGCLS_MAX_WEIGHT = 65536.0   # DPC_NEGCLS_MAX_WEIGHT
+
+
+def neg_class_weights(weights) -> tuple:
+    """(w_S, w_T, w_E) as the three float32 values the launcher sees; ValueError for what it would refuse"""
+    try:
+        w = tuple(float(x) for x in weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"negative-class weights must be three numbers (spatial, temporal, easy), got {weights!r}") from None
+    if len(w) != 3:
+        raise ValueError(f"negative-class weights must be three numbers (spatial, temporal, easy), got {weights!r}")
+    for x in w:
+        if not (x == x and 0.0 <= x <= NEGCLS_MAX_WEIGHT):
+            raise ValueError(f"negative-class weights must be finite and within [0, {NEGCLS_MAX_WEIGHT:g}], got {weights!r}")
+    return tuple(C.c_float(x).value for x in w)
+
+
 class ConvEpilogue(C.Structure):
     """struct dpc_conv_epilogue (include/dpc_hip.h)"""
     _fields_ = [(n, C.c_void_p) for n in ("addend", "addend_mask", "bn_raw", "bn_mask", "bn_mean", "bn_invstd", "stats")]
@@ -242,6 +265,8 @@ _SIGS = {
     "dpc_negq_bwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "dpc_ce_topk_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "dpc_ce_topk_bf16_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    "dpc_ce_topk_cls": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, NegClasses, _vp, _vp, _vp],
+    "dpc_ce_topk_bf16_cls": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, NegClasses, _vp, _vp, _vp],
     "dpc_rownorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
     "dpc_rownorm_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
     "dpc_bn_finalize_running": [_vp, _i32, _i32, _f64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp],

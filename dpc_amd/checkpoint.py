@@ -215,6 +215,18 @@ def check_neg_queue(eng, ck: dict, path: str) -> None:
         warnings.warn(f"{path} was written with a negative queue of {int(ck.get('neg_queue', 0))} batches, this run continues with {k}")
 
 
+def check_neg_weight(eng, ck: dict, path: str) -> None:
+    """the class weights of the training loss are a loss knob, not the model: a resumed run takes them from the flags or the caller, and
+    there is one warning if the file was written under others.  A file without the entry (every run's at weights 1, 1, 1) counts as
+    (1, 1, 1)."""
+    w = tuple(getattr(eng, "neg_classes", ((1.0, 1.0, 1.0), False))[0])
+    e = ck.get("neg_weight") or {}
+    was = (float(e.get("spatial", 1.0)), float(e.get("temporal", 1.0)), float(e.get("easy", 1.0)))
+    if was != w:
+        warnings.warn(f"{path} was written with the negative-class weights spatial {was[0]:g} temporal {was[1]:g} easy {was[2]:g}, this run "
+                      f"continues with spatial {w[0]:g} temporal {w[1]:g} easy {w[2]:g}")
+
+
 def check_score_norm(eng, ck: dict, path: str) -> None:
     """the form of the score is part of the model: a file written under another form or temperature than the run's is another model,
     whose loss and validation numbers do not continue this one's -- an error, not a warning.  A file without the entry (every run's
@@ -231,7 +243,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
     """the dictionary of dpc/main.py:167-172 (epoch = the NEXT epoch to run, as the reference stores epoch+1); with the learning-rate
     schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
     rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'; with the negative queue on,
-    plus 'neg_queue' (its slot count -- the bank is not in the file); under the cosine score, plus 'score_norm' ({'kind', 'temperature'}).  Refused while an
+    plus 'neg_queue' (its slot count -- the bank is not in the file); with class weights other than (1, 1, 1) in the loss, plus
+    'neg_weight' ({'spatial', 'temporal', 'easy'}); under the cosine score, plus 'score_norm' ({'kind', 'temperature'}).  Refused while an
     accumulation cycle is open: the sum so far is not part of the file"""
     eng._not_swapped("build_state")
     eng._not_mid_cycle("build_state")
@@ -247,6 +260,9 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
         state["accum_steps"] = eng.accum_steps
     if getattr(eng, "neg_queue", 0) > 0:   # the slot count only: the bank itself is never written
         state["neg_queue"] = eng.neg_queue
+    nw = tuple(getattr(eng, "neg_classes", ((1.0, 1.0, 1.0), False))[0])
+    if nw != (1.0, 1.0, 1.0):
+        state["neg_weight"] = {"spatial": nw[0], "temporal": nw[1], "easy": nw[2]}
     if getattr(eng, "score_norm", ("dot", 1.0))[0] != "dot":
         state["score_norm"] = {"kind": eng.score_norm[0], "temperature": eng.score_norm[1]}
     return state
@@ -315,6 +331,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
     check_optimizer_kind(eng, ck, path)
     check_accum_steps(eng, ck, path)
     check_neg_queue(eng, ck, path)   # (load_params above has emptied the bank)
+    check_neg_weight(eng, ck, path)
     if check_schedule:
         check_lr_schedule(eng, ck, path)
     info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}

@@ -1753,6 +1753,9 @@ class BackboneEngine:
         # ... and with the cosine score its form and temperature (only then)
         if getattr(self, "_snorm", None) is not None:
             base = base + (("score_norm", "cosine", self._snorm[0]),)
+        # ... and with the negative classes their weights and the report flag (only then)
+        if getattr(self, "_ncls", None) is not None:
+            base = base + (("neg_cls",) + self._ncls,)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
@@ -2087,6 +2090,10 @@ class DPCEngine(BackboneEngine):
         self._snorm = None        # the cosine score (set_score_norm): None, or (temperature, float32(1 / temperature))
         self.pred_n = self.finf_n = self.rnorm = None   # ... its normalised operands [R][D] and the rows' 1 / norm, f32 [2R]
         self._snorm_retired = []
+        self._ncls = None         # negative classes in the loss (set_neg_classes): None, or (w_S, w_T, w_E, report)
+        self._ncls_live = False   # the last forward was the training step's: loss_topk runs the _cls entry
+        self._ncls_desc = self._ncls_rows = self._ncls_report = None
+        self._ncls_retired = []
         self._need_wgrad(R, R, D)
         nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
         self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
@@ -2111,7 +2118,9 @@ class DPCEngine(BackboneEngine):
         materialise=False (bf16 mode): the score is consumed tile by tile by the fused loss (csrc/score_fused.hip) and
         never written; the return value is None and loss_topk() / backward() use the fused path.
         use_neg_queue: the engine-owned training step's forward (_forward_loss(train=True)) -- with set_neg_queue(K > 0) the rows also
-        compete against the bank's keys, and this forward's backward pushes feat_inf; everything else leaves the bank alone."""
+        compete against the bank's keys, and this forward's backward pushes feat_inf; everything else leaves the bank alone.  The same
+        flag marks the forward whose loss carries the class weights and the report of set_neg_classes: both belong to the engine-owned
+        training loss and to nothing else."""
         B, N, P, SQ, D, M = self.B, self.N, self.P, self.SQ, self.D, self.M
         if block is not None:
             if tuple(block.shape) != (B, N, 3, self.SL, self.size, self.size) or block.dtype != torch.float32:
@@ -2154,6 +2163,7 @@ class DPCEngine(BackboneEngine):
         self._score16_live = bool(self.score16 is not None and not materialise)
         # the negative queue: only the engine-owned training step (_forward_loss(train=True)) reads it
         self._negq_live = bool(self._negq and use_neg_queue)
+        self._ncls_live = bool(self._ncls is not None and use_neg_queue)   # (the engine-owned training forward: see the docstring)
         if self._score16_live:   # nobody reads the score but the loss: logits in the compute dtype
             self.score_mode = "materialised (bf16 logits)"
             with self.tag("score"):
@@ -2190,6 +2200,17 @@ class DPCEngine(BackboneEngine):
         R = self.R
         if self._score_fused:  # per-row (loss term, rank) pairs are already there; d/dscore is recomputed inside the backward
             self.call("dpc_ce_finalize", self.row_ws, R, self.result)
+            return self.result
+        if self._ncls_live:   # the same row kernels with a weight per negative class, with or without the bank (csrc/loss_cls.hip)
+            qs, lse = (self._negq_stats, self._negq_lse) if self._negq_live else (None, None)
+            rows, rep = (self._ncls_rows, self._ncls_report) if self._ncls[3] else (None, None)
+            with self.tag("score"):
+                if self._score16_live:
+                    self.call("dpc_ce_topk_bf16_cls", self.score16, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              self.ld_d, qs, lse, self._ncls_desc, rows, rep)
+                else:
+                    self.call("dpc_ce_topk_cls", self.score, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              L.dtype_code(self.cdtype), self.ld_d, qs, lse, self._ncls_desc, rows, rep)
             return self.result
         if self._negq_live:   # the same row kernels with the queue's statistics folded in (csrc/loss.hip: the EXT arms)
             with self.tag("score"):
@@ -2331,6 +2352,8 @@ class DPCEngine(BackboneEngine):
             raise L.DpcError(f"set_neg_queue: the feature size must be 256 or 32, not {self.D}")
         if self._score_path == "fused":
             raise L.DpcError('set_neg_queue: not with score_path="fused" (the benchmark arm of the in-batch score)')
+        if self._ncls is not None and self._ncls[2] == 0.0:
+            raise L.DpcError("set_neg_queue: the bank's keys are easy negatives, and set_neg_classes gave the easy class the weight 0")
         R, D = self.R, self.D
         pitch = L.negq_pitch(R)
         nf, nb = C.c_int64(0), C.c_int64(0)
@@ -2358,6 +2381,58 @@ class DPCEngine(BackboneEngine):
         if self._negq:
             self._negq_state.zero_()
         self._negq_live = False
+
+    # ------------------------------------------------------------------ negative classes in the loss (csrc/loss_cls.hip)
+    def set_neg_classes(self, weights=(1, 1, 1), report: bool = False):
+        """A weight per class of negatives inside the training loss's softmax, and a per-class report of where its mass sits.  The
+        classes are those of the reference's mask (dpc/model_3d.py:86-96, dpc_mask_gen) for row (b, p, s) and column (b2, n, s2):
+        spatial (same video, another position), temporal (same video and position, another predicted step), easy (another video; the
+        negative queue's keys are easy).  With ``weights = (w_S, w_T, w_E)`` a row's term is log Z - target with
+        Z = e^target + sum w_class e^logit, and d score = (w e^logit / Z - onehot) / R: a class of weight 0 is out of the loss and
+        gets a gradient of exactly 0.  Top-1/3/5 stay the unweighted ranks, so accuracies compare across weights.
+
+        ``report=True`` keeps, per training step, the means over the rows of the four shares of Z (positive, spatial, temporal, easy)
+        and the fraction of rows with at least one column of a class strictly above the target: neg_class_stats().
+
+        Only the engine-owned training forward (train_step, its micro-batches, the captured steps) runs the weighted entry;
+        forward(train=False), validate, capture_eval_step, forward(materialise=True) and the module boundary run what they ran.
+        Weights (1, 1, 1) without the report turn it off: the step runs the lines and launches it ran.  Refused: weights that are not
+        three finite numbers in [0, 65536], w_E = 0 with a negative queue, score_path="fused", inside a capture, in the middle of an
+        accumulation cycle.  The weights and the flag are among the scalars a captured step bakes in."""
+        w = L.neg_class_weights(weights)
+        report = bool(report)
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.DpcError("set_neg_classes: not while a graph is being captured")
+        self._not_mid_cycle("set_neg_classes")
+        on = report or w != (1.0, 1.0, 1.0)
+        if on and self._score_path == "fused":
+            raise L.DpcError('set_neg_classes: not with score_path="fused" (its loss is formed inside the contraction)')
+        if on and self._negq and w[2] == 0.0:
+            raise L.DpcError("set_neg_classes: the easy class cannot have the weight 0 while a negative queue is on (its keys are easy)")
+        if report and self._ncls_rows is None:
+            self._ncls_rows = torch.zeros((self.R, 8), dtype=torch.float32, device=self.device)
+            self._ncls_report = torch.zeros((8,), dtype=torch.float32, device=self.device)
+        if not report and self._ncls_rows is not None:   # the report's buffers go; a parked graph never points at freed memory
+            if self._capture_graphs:
+                self._ncls_retired.append((self._ncls_rows, self._ncls_report))
+            self._ncls_rows = self._ncls_report = None
+        self._ncls = (w[0], w[1], w[2], report) if on else None
+        self._ncls_desc = L.NegClasses(self.B, self.P, self.SQ, 0, w[0], w[1], w[2], 0.0) if on else None
+        self._ncls_live = False
+
+    @property
+    def neg_classes(self):
+        """((w_S, w_T, w_E), report) of the training loss: ((1.0, 1.0, 1.0), False) while off"""
+        return ((1.0, 1.0, 1.0), False) if self._ncls is None else (self._ncls[:3], self._ncls[3])
+
+    NEG_CLASS_KEYS = ("mass_pos", "mass_S", "mass_T", "mass_E", "above_S", "above_T", "above_E")
+
+    def neg_class_stats(self) -> Dict[str, float]:
+        """the report of the last training step (micro-batch): one 32-byte read-back, a host synchronisation"""
+        if self._ncls is None or not self._ncls[3]:
+            raise L.DpcError("neg_class_stats: the report is off (set_neg_classes(..., report=True))")
+        v = self._ncls_report.cpu().tolist()
+        return dict(zip(self.NEG_CLASS_KEYS, v[:7]))
 
     # ------------------------------------------------------------------ cosine score (csrc/score_norm.hip)
     def set_score_norm(self, kind: str = "dot", temperature: float = 1.0):
@@ -2411,6 +2486,7 @@ class DPCEngine(BackboneEngine):
         super().release_captures()
         self._negq_retired.clear()   # no capture of this engine is left to replay on an earlier ring
         self._snorm_retired.clear()
+        self._ncls_retired.clear()
 
     def load_params(self, params: Dict[str, torch.Tensor]):
         super().load_params(params)

@@ -86,6 +86,12 @@ def build_parser() -> argparse.ArgumentParser:
                         'training batches stay on the GPU and are extra negatives of every training row (engine.set_neg_queue): the loss '
                         'and the printed training accuracies are then over R + K R candidates.  A memory bank -- keys up to K updates old, '
                         'no momentum encoder; per GPU; not checkpointed; validation never uses it.  1 .. 64, bf16 only.  0: off')
+    parser.add_argument('--neg_weight', default='1,1,1', type=str, metavar='S,T,E', help='weights of the three classes of negatives inside the '
+                        'training loss\'s softmax (engine.set_neg_classes): spatial (same video, another position), temporal (same video and '
+                        'position, another predicted step), easy (another video, and the --neg_queue keys).  0 takes a class out of the '
+                        'loss.  The printed accuracies stay the unweighted ranks; validation is never weighted.  Each within [0, 65536]')
+    parser.add_argument('--neg_report', action='store_true', help='end every printed training line with the mean shares of the softmax mass '
+                        '(positive / spatial / temporal / easy) and the fraction of rows with a column of each class above the target')
     parser.add_argument('--score_norm', default='dot', choices=['dot', 'cosine'], help='form of the contrastive score (engine.set_score_norm): '
                         'dot = pred . feature_inf, the reference\'s; cosine = the L2-normalised operands over --temperature, every logit in '
                         '[-1/T, 1/T] (training and validation alike).  Another model: loss and accuracies compare between runs of one T only')
@@ -156,6 +162,11 @@ def _worker(rank: int, world: int, args, port: int):
         eng.set_neg_queue(args.neg_queue)
         if rank == 0:
             print('Negative queue: {0} batches ({1} keys of {2}, per GPU)'.format(args.neg_queue, args.neg_queue * eng.R, eng.D), flush=True)
+    neg_w = parse_neg_weight(args.neg_weight)
+    if neg_w != (1.0, 1.0, 1.0) or args.neg_report:   # --neg_weight / --neg_report: before --resume compares the file's weights, and before any capture
+        eng.set_neg_classes(neg_w, report=args.neg_report)
+        if rank == 0 and neg_w != (1.0, 1.0, 1.0):
+            print('Negative classes: spatial {0:g} temporal {1:g} easy {2:g}'.format(*neg_w), flush=True)
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -257,7 +268,8 @@ def _worker(rank: int, world: int, args, port: int):
                     a.update(v, per_gpu)
                 if train and rank == 0:
                     print('Epoch: [{0}][{1}/{2}]\t Loss {3:.6f} ({4:.4f})\t Acc: top1 {5:.4f}; top3 {6:.4f}; top5 {7:.4f} T:{8:.2f}\t'.format(
-                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else '') + (lr_tail() if lr_tail else ''), flush=True)
+                        epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else '') + (lr_tail() if lr_tail else '') +
+                        (neg_report_tail(eng) if args.neg_report else ''), flush=True)
                 if train:
                     iteration += 1
         line = steps.replay_line(args.batch_size)
@@ -303,6 +315,36 @@ def check_neg_queue_flags(args):
         raise ValueError('--neg_queue needs --dtype bf16 (f32 is the parity mode against a reference that has no bank)')
 
 
+def parse_neg_weight(text: str):
+    """'S,T,E' -> the three float32 weights; ValueError for anything the launcher would refuse"""
+    from . import _lib as L
+    parts = text.split(',')
+    try:
+        vals = [float(p) for p in parts]
+    except ValueError:
+        vals = []
+    if len(parts) != 3 or len(vals) != 3:
+        raise ValueError('--neg_weight takes three comma-separated numbers S,T,E (spatial, temporal, easy), got {0!r}'.format(text))
+    try:
+        return L.neg_class_weights(vals)
+    except ValueError as e:
+        raise ValueError('--neg_weight: {0}'.format(e)) from None
+
+
+def check_neg_class_flags(args):
+    """--neg_weight / --neg_report, refused before a rank starts"""
+    w = parse_neg_weight(args.neg_weight)
+    if args.neg_queue and w[2] == 0.0:
+        raise ValueError('--neg_weight: the easy class cannot have the weight 0 with --neg_queue (the bank\'s keys are easy negatives)')
+
+
+def neg_report_tail(eng) -> str:
+    """--neg_report: the tail of a printed training line (one 32-byte read-back)"""
+    s = eng.neg_class_stats()
+    return ' neg P/S/T/E {0:.3f}/{1:.3f}/{2:.3f}/{3:.3f} above S/T/E {4:.3f}/{5:.3f}/{6:.3f}'.format(
+        s['mass_pos'], s['mass_S'], s['mass_T'], s['mass_E'], s['above_S'], s['above_T'], s['above_E'])
+
+
 def check_score_flags(args):
     """--score_norm / --temperature, refused before a rank starts"""
     if not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -317,6 +359,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     check_ema_flags(args)
     check_accum_flags(args)
     check_neg_queue_flags(args)
+    check_neg_class_flags(args)
     check_score_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)

@@ -803,6 +803,35 @@ int dpc_ce_topk_ext(const float* score, int32_t rows, int32_t cols, int32_t ld, 
 int dpc_ce_topk_bf16_ext(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
                          int32_t ld_d, const float* qstats, float* lse_out, dpc_stream_t stream);
 
+/* ---- negative classes in the loss (csrc/loss_cls.hip): a weight per class of dpc_mask_gen inside the softmax, and a per-class report.
+ * Row r = (b, p, s), column c = (b2, n, s2), cols = B P SQ, W = P SQ; the class of (r, c) is dpc_mask_gen's value in closed form:
+ *   b != b2 easy (0) | b == b2, s != s2 spatial (-3) | b == b2, s == s2, n != p temporal (-1) | c == r positive (1); bank keys are easy.
+ *   Z_r = e^(s_rr) + sum_{c != r} w_class e^(s_rc) + w_easy sum_{q live} e^(pred_r . q);  row_ws[r] = (log Z_r - s_rr, rank);
+ *   dscore_rc = (w_class e^(s_rc) / Z_r - [c == r]) / rows: a class of weight 0 gets exactly 0.  The rank (and top-1/3/5) is the
+ *   unweighted count of strictly greater logits over all columns and the bank, as in the older entries.
+ * The argument lists of the _ext entries, with: qstats / lse_out NULL together (no bank); with a bank lse_out[r] = log Z_r - log w_easy,
+ * so that dpc_negq_bwd yields the weighted share unchanged; the descriptor by value; two optional outputs:
+ *   report_rows [rows][8] f32: the shares of Z_r (positive, spatial, temporal, easy -- the bank under easy; they sum to 1), the number
+ *                of columns of each negative class strictly above the target (they add up to the rank; rk_q under easy), 0;
+ *   report [8] f32 (needs report_rows): the means of the four shares, the fraction of rows whose count is not 0 per class, 0.
+ * DPC_ERR_ARG: cols != B P SQ, a weight that is not finite or outside [0, DPC_NEGCLS_MAX_WEIGHT], flags / reserved not 0, w_easy = 0
+ * with a bank, one of qstats / lse_out alone, report without report_rows.  Dispatch, DPC_ERR_UNSUPPORTED and every other argument
+ * error: those of dpc_ce_topk / dpc_ce_topk_bf16.  At weights (1, 1, 1) row_ws, result, dscore and lse_out are the older entries'
+ * bits.  The geometry comes from cols; rows may be fewer. */
+#define DPC_NEGCLS_MAX_WEIGHT 65536.0f
+typedef struct dpc_neg_classes {
+    int32_t B, P, SQ;
+    int32_t flags;      /* 0 */
+    float w_spatial, w_temporal, w_easy;
+    float reserved;     /* 0 */
+} dpc_neg_classes;          /* 32 bytes, by value */
+int dpc_ce_topk_cls(const float* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore, int32_t dtype_d,
+                    int32_t ld_d, const float* qstats, float* lse_out, dpc_neg_classes cls, float* report_rows, float* report,
+                    dpc_stream_t stream);
+int dpc_ce_topk_bf16_cls(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
+                         int32_t ld_d, const float* qstats, float* lse_out, dpc_neg_classes cls, float* report_rows, float* report,
+                         dpc_stream_t stream);
+
 /* ---- cosine score (csrc/score_norm.hip): L2 normalisation of the score's two operands in front of the contraction, and its backward.
  * Rows [R][D] of `dtype` (DPC_F32 / DPC_BF16), D = 256 or 32 (else DPC_ERR_UNSUPPORTED); one launch serves operand a and, when
  * xb != NULL, operand b (xb and yb / gb are NULL together).  rnorm is f32 [2R]: operand a's rows first, then b's.

@@ -48,7 +48,8 @@ for part in ("00_head.md", "04_kernels.md", "05_to_07.md", "08_on.md"):
     out += open(os.path.join(P, part)).read().rstrip() + "\n\n"
 for k, v in rep.items():
     out = out.replace(f"@{k}@", v)
-left = [w for w in out.split() if w.startswith("@") and w.endswith("@") and len(w) > 2]
+import re  # noqa: E402
+left = re.findall(r"@[A-Z][A-Z0-9_]*@", out)
 assert not left, left
 open(os.path.join(ROOT, "DESIGN.md"), "w").write(out.rstrip() + "\n")
 print(len(out), "bytes")
