@@ -267,6 +267,10 @@ _SIGS = {
     "dpc_ce_topk_bf16_ext": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
     "dpc_ce_topk_cls": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, NegClasses, _vp, _vp, _vp],
     "dpc_ce_topk_bf16_cls": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, NegClasses, _vp, _vp, _vp],
+    "dpc_ce_sym_ws_floats": [_i32, _i32, C.POINTER(_i64)],
+    "dpc_ce_colpass": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "dpc_ce_topk_sym": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "dpc_ce_topk_bf16_sym": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp],
     "dpc_rownorm_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
     "dpc_rownorm_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _vp],
     "dpc_bn_finalize_running": [_vp, _i32, _i32, _f64, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp],

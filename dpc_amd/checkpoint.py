@@ -227,6 +227,15 @@ def check_neg_weight(eng, ck: dict, path: str) -> None:
                       f"continues with spatial {w[0]:g} temporal {w[1]:g} easy {w[2]:g}")
 
 
+def check_loss_sym(eng, ck: dict, path: str) -> None:
+    """the weight of the symmetric loss's column direction is a property of the loss, not of the model: a resumed run takes it from the
+    flags or the caller, and there is one warning if the file was written under another.  A file without the entry counts as 0."""
+    w = float(getattr(eng, "loss_sym", 0.0))
+    was = float(ck.get("loss_sym", 0.0))
+    if was != w:
+        warnings.warn(f"{path} was written with the symmetric-loss weight {was:g}, this run continues with {w:g}")
+
+
 def check_score_norm(eng, ck: dict, path: str) -> None:
     """the form of the score is part of the model: a file written under another form or temperature than the run's is another model,
     whose loss and validation numbers do not continue this one's -- an error, not a warning.  A file without the entry (every run's
@@ -244,7 +253,7 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
     schedule on, plus 'lr_schedule' (lr_schedule_entry); with the parameter average on, plus 'ema' (ema_entry); under another update
     rule than Adam, plus 'optimizer_kind' ("adamw" / "lamb"); under gradient accumulation, plus 'accum_steps'; with the negative queue on,
     plus 'neg_queue' (its slot count -- the bank is not in the file); with class weights other than (1, 1, 1) in the loss, plus
-    'neg_weight' ({'spatial', 'temporal', 'easy'}); under the cosine score, plus 'score_norm' ({'kind', 'temperature'}).  Refused while an
+    'neg_weight' ({'spatial', 'temporal', 'easy'}); under the symmetric loss, plus 'loss_sym' (its weight); under the cosine score, plus 'score_norm' ({'kind', 'temperature'}).  Refused while an
     accumulation cycle is open: the sum so far is not part of the file"""
     eng._not_swapped("build_state")
     eng._not_mid_cycle("build_state")
@@ -263,6 +272,8 @@ def build_state(eng, epoch: int, net: str, best_acc: float, iteration: int) -> d
     nw = tuple(getattr(eng, "neg_classes", ((1.0, 1.0, 1.0), False))[0])
     if nw != (1.0, 1.0, 1.0):
         state["neg_weight"] = {"spatial": nw[0], "temporal": nw[1], "easy": nw[2]}
+    if getattr(eng, "loss_sym", 0.0) > 0:
+        state["loss_sym"] = float(eng.loss_sym)
     if getattr(eng, "score_norm", ("dot", 1.0))[0] != "dot":
         state["score_norm"] = {"kind": eng.score_norm[0], "temperature": eng.score_norm[1]}
     return state
@@ -332,6 +343,7 @@ def resume(eng, path: str, reset_lr: bool = False, check_schedule: bool = True) 
     check_accum_steps(eng, ck, path)
     check_neg_queue(eng, ck, path)   # (load_params above has emptied the bank)
     check_neg_weight(eng, ck, path)
+    check_loss_sym(eng, ck, path)
     if check_schedule:
         check_lr_schedule(eng, ck, path)
     info = {"epoch": ck["epoch"], "iteration": ck.get("iteration", 0), "best_acc": ck.get("best_acc", 0.0)}

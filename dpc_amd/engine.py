@@ -1756,6 +1756,9 @@ class BackboneEngine:
         # ... and with the negative classes their weights and the report flag (only then)
         if getattr(self, "_ncls", None) is not None:
             base = base + (("neg_cls",) + self._ncls,)
+        # ... and with the symmetric loss the weight of its column direction (only then)
+        if getattr(self, "_sym", 0.0) > 0:
+            base = base + (("loss_sym", self._sym),)
         # ... and with the learning-rate schedule its descriptor, which a captured step carries by value (only then, once more)
         return base + (("lr_schedule", bytes(self._lr_desc)),) if self._lr_desc is not None else base
 
@@ -2094,6 +2097,10 @@ class DPCEngine(BackboneEngine):
         self._ncls_live = False   # the last forward was the training step's: loss_topk runs the _cls entry
         self._ncls_desc = self._ncls_rows = self._ncls_report = None
         self._ncls_retired = []
+        self._sym = 0.0           # symmetric loss (set_loss_sym): the weight W of the key-to-prediction direction, 0 = off
+        self._sym_live = False    # the last forward was the training step's: loss_topk runs the _sym entry
+        self._sym_col_lse = self._sym_col_ws = self._sym_ws = self._sym_result = None
+        self._sym_retired = []
         self._need_wgrad(R, R, D)
         nsk = C.c_int32(0)  # d_pred = dS @ feature_inf: f32 slabs of the split reduction
         self.lib.call("dpc_gemm_nt_splitk", L.dtype_code(dt), R, D, self.ld_d, None, self.ld_d, None, self.ld_d, None, C.byref(nsk), self.lib.stream())
@@ -2164,6 +2171,7 @@ class DPCEngine(BackboneEngine):
         # the negative queue: only the engine-owned training step (_forward_loss(train=True)) reads it
         self._negq_live = bool(self._negq and use_neg_queue)
         self._ncls_live = bool(self._ncls is not None and use_neg_queue)   # (the engine-owned training forward: see the docstring)
+        self._sym_live = bool(self._sym > 0 and use_neg_queue)             # (the same rule for the symmetric loss: set_loss_sym)
         if self._score16_live:   # nobody reads the score but the loss: logits in the compute dtype
             self.score_mode = "materialised (bf16 logits)"
             with self.tag("score"):
@@ -2200,6 +2208,17 @@ class DPCEngine(BackboneEngine):
         R = self.R
         if self._score_fused:  # per-row (loss term, rank) pairs are already there; d/dscore is recomputed inside the backward
             self.call("dpc_ce_finalize", self.row_ws, R, self.result)
+            return self.result
+        if self._sym_live:    # the column direction beside the row direction, with or without the bank (csrc/loss_sym.hip)
+            qs, lse = (self._negq_stats, self._negq_lse) if self._negq_live else (None, None)
+            tail = (qs, lse, self._sym, 0, self._sym_col_lse, self._sym_col_ws, self._sym_ws, self._sym_result)
+            with self.tag("score"):
+                if self._score16_live:
+                    self.call("dpc_ce_topk_bf16_sym", self.score16, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              self.ld_d, *tail)
+                else:
+                    self.call("dpc_ce_topk_sym", self.score, R, R, R, self.row_ws, self.result, self.dscore if with_grad else None,
+                              L.dtype_code(self.cdtype), self.ld_d, *tail)
             return self.result
         if self._ncls_live:   # the same row kernels with a weight per negative class, with or without the bank (csrc/loss_cls.hip)
             qs, lse = (self._negq_stats, self._negq_lse) if self._negq_live else (None, None)
@@ -2405,6 +2424,8 @@ class DPCEngine(BackboneEngine):
             raise L.DpcError("set_neg_classes: not while a graph is being captured")
         self._not_mid_cycle("set_neg_classes")
         on = report or w != (1.0, 1.0, 1.0)
+        if on and self._sym > 0:
+            raise L.DpcError("set_neg_classes: not with the symmetric loss (set_loss_sym): the column direction of the class weights is not built")
         if on and self._score_path == "fused":
             raise L.DpcError('set_neg_classes: not with score_path="fused" (its loss is formed inside the contraction)')
         if on and self._negq and w[2] == 0.0:
@@ -2433,6 +2454,63 @@ class DPCEngine(BackboneEngine):
             raise L.DpcError("neg_class_stats: the report is off (set_neg_classes(..., report=True))")
         v = self._ncls_report.cpu().tolist()
         return dict(zip(self.NEG_CLASS_KEYS, v[:7]))
+
+    # ------------------------------------------------------------------ symmetric loss (csrc/loss_sym.hip)
+    def set_loss_sym(self, w: float = 0.0):
+        """The symmetric InfoNCE: over the same [R][R] logits each key (a column) also picks its prediction among the rows, the second
+        half of the loss CLIP, NT-Xent and MoCo v3 train with.  With ``w`` in (0, 1]
+
+            loss = (1 - w) mean_i Lr_i + w mean_j Lc_j,   Lc_j = logsumexp(S[:, j]) - S[j, j]
+
+        Lr_i the row direction as it was (the negative queue in its denominator; the bank has keys but no predictions and takes no part
+        in the column direction), and d score = ((1 - w)(pr - I) + w (pc - I)) / R, rounded once.  w = 0.5 is the symmetric loss.
+        ``result`` keeps the row top-1/3/5, so accuracies compare across runs; loss_sym_stats() reads the two means and the column
+        accuracies.  Everything behind ``dscore`` is what it was.
+
+        Only the engine-owned training forward (train_step, its micro-batches, the captured steps) runs the symmetric entry;
+        forward(train=False), validate, capture_eval_step, forward(materialise=True) and the module boundary run what they ran.
+        w = 0 turns it off and frees the buffers: the step runs the lines and launches it ran.  Refused: w outside [0, 1] or not
+        finite, score_path="fused", together with set_neg_classes (in either order), inside a capture, in the middle of an accumulation
+        cycle.  w is among the scalars a captured step bakes in."""
+        try:
+            w = float(w)
+        except (TypeError, ValueError):
+            raise ValueError(f"set_loss_sym: the weight must be a number in [0, 1], got {w!r}") from None
+        if not (math.isfinite(w) and 0.0 <= w <= 1.0):
+            raise ValueError(f"set_loss_sym: the weight must be a number in [0, 1], got {w!r}")
+        w = C.c_float(w).value   # the float32 the launcher sees
+        if self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise L.DpcError("set_loss_sym: not while a graph is being captured")
+        self._not_mid_cycle("set_loss_sym")
+        if w > 0 and self._score_path == "fused":
+            raise L.DpcError('set_loss_sym: not with score_path="fused" (its loss is formed inside the contraction)')
+        if w > 0 and self._ncls is not None:
+            raise L.DpcError("set_loss_sym: not with set_neg_classes: the column direction of the class weights is not built")
+        if w > 0 and self._sym_col_lse is None:
+            nf = C.c_int64(0)
+            self.lib.call("dpc_ce_sym_ws_floats", self.R, 0, C.byref(nf))
+            self._sym_col_lse = self.empty((self.R,), torch.float32)
+            self._sym_col_ws = self.empty((self.R, 2), torch.float32)
+            self._sym_ws = self.empty((nf.value,), torch.float32)
+            self._sym_result = torch.zeros((8,), dtype=torch.float32, device=self.device)
+        if w == 0 and self._sym_col_lse is not None:   # the buffers go; a parked graph never points at freed memory
+            if self._capture_graphs:
+                self._sym_retired.append((self._sym_col_lse, self._sym_col_ws, self._sym_ws, self._sym_result))
+            self._sym_col_lse = self._sym_col_ws = self._sym_ws = self._sym_result = None
+        self._sym, self._sym_live = w, False
+
+    @property
+    def loss_sym(self) -> float:
+        """the weight of the key-to-prediction direction of the training loss (0.0: off)"""
+        return self._sym
+
+    LOSS_SYM_KEYS = ("loss_row", "loss_col", "col_top1", "col_top3", "col_top5")
+
+    def loss_sym_stats(self) -> Dict[str, float]:
+        """the two directions of the last training step (micro-batch): one 32-byte read-back, a host synchronisation"""
+        if not self._sym > 0:
+            raise L.DpcError("loss_sym_stats: the symmetric loss is off (set_loss_sym(w > 0))")
+        return dict(zip(self.LOSS_SYM_KEYS, self._sym_result.cpu().tolist()[:5]))
 
     # ------------------------------------------------------------------ cosine score (csrc/score_norm.hip)
     def set_score_norm(self, kind: str = "dot", temperature: float = 1.0):
@@ -2487,6 +2565,7 @@ class DPCEngine(BackboneEngine):
         self._negq_retired.clear()   # no capture of this engine is left to replay on an earlier ring
         self._snorm_retired.clear()
         self._ncls_retired.clear()
+        self._sym_retired.clear()
 
     def load_params(self, params: Dict[str, torch.Tensor]):
         super().load_params(params)

@@ -92,6 +92,11 @@ def build_parser() -> argparse.ArgumentParser:
                         'loss.  The printed accuracies stay the unweighted ranks; validation is never weighted.  Each within [0, 65536]')
     parser.add_argument('--neg_report', action='store_true', help='end every printed training line with the mean shares of the softmax mass '
                         '(positive / spatial / temporal / easy) and the fraction of rows with a column of each class above the target')
+    parser.add_argument('--loss_sym', default=0.0, type=float, metavar='W', help='symmetric InfoNCE (engine.set_loss_sym): over the same logits '
+                        'each key also picks its prediction among the rows, and the training loss is (1 - W) x the prediction-to-key term + W x '
+                        'the key-to-prediction term; 0.5 is the symmetric loss of CLIP / NT-Xent.  Every printed training line then ends in the '
+                        'two terms and the column top-1; the printed accuracies stay the row ranks; validation is never symmetric.  Within '
+                        '[0, 1]; not with --neg_weight / --neg_report.  0: off')
     parser.add_argument('--score_norm', default='dot', choices=['dot', 'cosine'], help='form of the contrastive score (engine.set_score_norm): '
                         'dot = pred . feature_inf, the reference\'s; cosine = the L2-normalised operands over --temperature, every logit in '
                         '[-1/T, 1/T] (training and validation alike).  Another model: loss and accuracies compare between runs of one T only')
@@ -167,6 +172,10 @@ def _worker(rank: int, world: int, args, port: int):
         eng.set_neg_classes(neg_w, report=args.neg_report)
         if rank == 0 and neg_w != (1.0, 1.0, 1.0):
             print('Negative classes: spatial {0:g} temporal {1:g} easy {2:g}'.format(*neg_w), flush=True)
+    if args.loss_sym > 0:                  # --loss_sym: before --resume compares the file's weight with the run's, and before any capture
+        eng.set_loss_sym(args.loss_sym)
+        if rank == 0:
+            print('Loss: symmetric, key-to-prediction weight {0:g}'.format(args.loss_sym), flush=True)
     if args.resume:  # dpc/main.py:88-102: strict model load + optimizer state (unless --reset_lr)
         if os.path.isfile(args.resume):
             m = re.search('_lr(.+?)_', args.resume)
@@ -269,7 +278,7 @@ def _worker(rank: int, world: int, args, port: int):
                 if train and rank == 0:
                     print('Epoch: [{0}][{1}/{2}]\t Loss {3:.6f} ({4:.4f})\t Acc: top1 {5:.4f}; top3 {6:.4f}; top5 {7:.4f} T:{8:.2f}\t'.format(
                         epoch, idx, n_batches, loss, losses.local_avg, t1, t3, t5, time.time() - tic) + (guard.gnorm() if guard else '') + (lr_tail() if lr_tail else '') +
-                        (neg_report_tail(eng) if args.neg_report else ''), flush=True)
+                        (neg_report_tail(eng) if args.neg_report else '') + (loss_sym_tail(eng) if args.loss_sym > 0 else ''), flush=True)
                 if train:
                     iteration += 1
         line = steps.replay_line(args.batch_size)
@@ -345,6 +354,20 @@ def neg_report_tail(eng) -> str:
         s['mass_pos'], s['mass_S'], s['mass_T'], s['mass_E'], s['above_S'], s['above_T'], s['above_E'])
 
 
+def check_loss_sym_flags(args):
+    """--loss_sym, refused before a rank starts"""
+    if not (math.isfinite(args.loss_sym) and 0.0 <= args.loss_sym <= 1.0):
+        raise ValueError('--loss_sym must be a weight within [0, 1]')
+    if args.loss_sym > 0 and (parse_neg_weight(args.neg_weight) != (1.0, 1.0, 1.0) or args.neg_report):
+        raise ValueError('--loss_sym: not with --neg_weight / --neg_report (the column direction of the class weights is not built)')
+
+
+def loss_sym_tail(eng) -> str:
+    """--loss_sym: the tail of a printed training line (one 32-byte read-back)"""
+    s = eng.loss_sym_stats()
+    return ' Lr {0:.4f} Lc {1:.4f} c@1 {2:.4f}'.format(s['loss_row'], s['loss_col'], s['col_top1'])
+
+
 def check_score_flags(args):
     """--score_norm / --temperature, refused before a rank starts"""
     if not (math.isfinite(args.temperature) and args.temperature > 0):
@@ -360,6 +383,7 @@ def main(argv=None, _simulator=None, _widths=None, _probe=None):
     check_accum_flags(args)
     check_neg_queue_flags(args)
     check_neg_class_flags(args)
+    check_loss_sym_flags(args)
     check_score_flags(args)
     check_schedule_flags(args, 0 if args.frames else args.synthetic // args.accum_steps)
     check_optimizer_flags(args)

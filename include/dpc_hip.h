@@ -832,6 +832,35 @@ int dpc_ce_topk_bf16_cls(const void* score, int32_t rows, int32_t cols, int32_t 
                          int32_t ld_d, const float* qstats, float* lse_out, dpc_neg_classes cls, float* report_rows, float* report,
                          dpc_stream_t stream);
 
+/* ---- symmetric InfoNCE (csrc/loss_sym.hip): over the square logits S [R][R] each key (column) also picks its prediction among the
+ * rows.  With a = 1 - w, b = w (f32):
+ *   Lr_i = logsumexp(S[i, :], bank) - S[i, i]   (the row direction: dpc_ce_topk[_bf16][_ext]'s)
+ *   Lc_j = logsumexp(S[:, j]) - S[j, j]         (the bank has keys but no predictions: it takes no part)
+ *   result      = (a mean Lr + b mean Lc, row top-1, top-3, top-5)          row_ws[i] = (Lr_i, rank_i) as ever
+ *   sym_result  = (mean Lr, mean Lc, column top-1, top-3, top-5, 0, 0, 0)   col_ws[j] = (Lc_j, #{i : S[i, j] > S[j, j]})
+ *   dscore[i,j] = (a (pr[i, j] - [i == j]) + b (exp(S[i, j] - col_lse[j]) - [i == j])) / R, rounded once into dscore's dtype
+ * dpc_ce_colpass is the column direction alone: col_lse [R] (16-byte aligned for the _sym entries) and col_ws [R][2] of a row-major
+ * matrix of dtype_s (DPC_F32 / DPC_BF16), `fast` = 1 with v_exp_f32 exponentials, 0 with expf; rows behind R and columns in [R, ld)
+ * are never read; shapes without whole 16-byte units (R or ld no multiple of 4 / 8, a misaligned pointer) take a scalar form.  Two
+ * launches, no atomics, a fixed order of every sum: same inputs, same bits.  `slabs` = 0 lets the library cut the rows (the rule that
+ * fills the device), > 0 asks for that many slabs (fewer where R is short); ws holds dpc_ce_sym_ws_floats(R, slabs) floats, which
+ * returns the largest slab count any layout takes.
+ * The _sym entries run the column pass, the row kernel their sibling's dispatch selects, and the finalize: four launches.  The
+ * sibling's argument list (qstats / lse_out NULL together: no bank) plus w, slabs and the four buffers.  With a bank lse_out[i] =
+ * lse_i - log a (1e38 at a = 0), so that dpc_negq_bwd yields a x the bank's share unchanged.  DPC_ERR_ARG: rows != cols,
+ * w outside [0, 1] or not finite, a NULL or (col_lse) misaligned buffer, one of qstats / lse_out alone, and the sibling's argument
+ * errors; DPC_ERR_UNSUPPORTED: the sibling's.  Nothing is launched then.  At w = 0 row_ws, result, dscore and lse_out are the
+ * sibling's bits. */
+int dpc_ce_sym_ws_floats(int32_t R, int32_t slabs, int64_t* floats);
+int dpc_ce_colpass(const void* score, int32_t dtype_s, int32_t R, int32_t ld, int32_t fast, int32_t slabs, float* col_lse, float* col_ws,
+                   float* ws, dpc_stream_t stream);
+int dpc_ce_topk_sym(const float* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore, int32_t dtype_d,
+                    int32_t ld_d, const float* qstats, float* lse_out, float w, int32_t slabs, float* col_lse, float* col_ws, float* ws,
+                    float* sym_result, dpc_stream_t stream);
+int dpc_ce_topk_bf16_sym(const void* score, int32_t rows, int32_t cols, int32_t ld, float* row_ws, float* result, void* dscore,
+                         int32_t ld_d, const float* qstats, float* lse_out, float w, int32_t slabs, float* col_lse, float* col_ws, float* ws,
+                         float* sym_result, dpc_stream_t stream);
+
 /* ---- cosine score (csrc/score_norm.hip): L2 normalisation of the score's two operands in front of the contraction, and its backward.
  * Rows [R][D] of `dtype` (DPC_F32 / DPC_BF16), D = 256 or 32 (else DPC_ERR_UNSUPPORTED); one launch serves operand a and, when
  * xb != NULL, operand b (xb and yb / gb are NULL together).  rnorm is f32 [2R]: operand a's rows first, then b's.
